@@ -56,6 +56,8 @@ def parse():
     ap.add_argument("--wide-chunk", type=int, default=512, help="side leg: prefill in chunks of this many tokens (0: skip)")
     ap.add_argument("--super-chunks", type=int, default=4, help="reference-sized prefill chunks (--batch tokens each) per launch sequence "
                     "(ps_hip_model_prefill: same bits as chunk-by-chunk forwards; 1: one forward per chunk)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed decode computed (DIR/<name>.npy): "
+                    "the ids of the K timed steps and the logits of the last one")
     return ap.parse_args()
 
 
@@ -64,7 +66,12 @@ def ensure_model(args, rank, barrier):
     wt = {"Q4_K_M": synth.Q4_K_M, "Q5_K_M": synth.Q5_K_M}.get(args.wtype) or gguf.NAME_TYPE[args.wtype]  # Q4_K_M / Q5_K_M: llama.cpp's per-tensor mixes with Q6_K
     d = args.model_dir or os.path.join(os.environ.get("TMPDIR", "/tmp"), f"ps_bench_{args.preset}_{args.wtype}_{args.seed}")
     marker = os.path.join(d, ".done")
-    if rank == 0 and not os.path.exists(marker):
+    # the cache directory is named by preset, type and seed only: a model written there for another --n-ctx (n_rope_ctx_orig follows it) is written anew,
+    # so that the same arguments always run on the same inputs
+    stale = rank == 0 and not args.model_dir and os.path.exists(marker) and synth.load_model_json(d)["llm_config"] != synth.llm_config(args.preset, args.n_ctx)
+    if rank == 0 and (not os.path.exists(marker) or stale):
+        if stale:
+            os.remove(marker)
         t0 = time.time()
         synth.write_model_dir(d, args.preset, wt, n_ctx=args.n_ctx, seed=args.seed)
         open(marker, "w").write("ok")
@@ -364,6 +371,14 @@ def fp16_kv_leg(ctx, model, args, prompt, ids_parity):
             "note": "fp16 K/V mirrors + split-KV online soft-max for single-token attention only; prefill reads the FP32 cache; not bit-exact by design"}
 
 
+def dump_outputs(out_dir, ids, logits):
+    """--dump-outputs: what the caller of the timed decode_greedy receives -- the ids of the K timed steps (float64: exact) -- and the
+    logits of its last step (float32, one vocabulary row: the row the device arg-max picked the last id from).  Under 1 MB for the 8B model."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "decode_ids.npy"), np.asarray(ids, dtype=np.float64))
+    np.save(os.path.join(out_dir, "last_step_logits.npy"), np.asarray(logits, dtype=np.float32))
+
+
 def gpu_short_run(model, p, ids_cpu):
     """the GPU on the CPU leg's short prompt, teacher-forced with the CPU's ids: logits of every step"""
     model.reset()
@@ -510,6 +525,8 @@ def main():
     ctx.sync(); barrier()
     dt = time.perf_counter() - t0
     dev_ms = ctx.elapsed_ms(e0, e1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ids, model.logits(1)[0])
     if dist is not None:
         dt, prefill_s, prefill_warm_s = max_over_ranks(dist, [dt, prefill_s, prefill_warm_s])
         replicas_agree, _ = gather_ids(dist, ids, world)
