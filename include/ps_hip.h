@@ -112,8 +112,9 @@ int ps_hip_event_elapsed_ms(ps_hip_ctx *ctx, void *ev_start, void *ev_stop, floa
 int ps_hip_event_destroy(ps_hip_ctx *ctx, void *ev);
 
 /* ------------------------------------------------------------------ weights */
-/* host_blocks: N rows of GGUF blocks of `dtype` (row stride = ggml_row_size(dtype, K)), or F32 rows.
- * The device copy is repacked into a structure-of-arrays layout private to the backend. */
+/* host_blocks: N rows of GGUF blocks of `dtype` (row stride = ggml_row_size(dtype, K)), or F32 / F16 rows (any K).
+ * The device copy of a quantized matrix is repacked into a structure-of-arrays layout private to the backend; F32 / F16 rows are kept as they are.
+ * F16 mat-muls follow ggml_vec_dot_f16 (activation rounded by ggml_fp32_to_fp16_row, n % 32 leftovers in double): bit-exact like the other types. */
 int ps_hip_weight_upload(ps_hip_ctx *ctx, int dtype, const void *host_blocks, int64_t K, int64_t N, ps_weight **out);
 void ps_hip_weight_free(ps_hip_ctx *ctx, ps_weight *w);
 /* GGUF bytes of the matrix = N * ggml_row_size(dtype, K): the roofline's algorithmic byte count */
@@ -123,8 +124,8 @@ int ps_hip_weight_dtype(const ps_weight *w);
 /* ------------------------------------------------------------------ op level (reference-shaped) */
 int ps_hip_vec_dot_type(int dtype);
 size_t ps_hip_row_size(int dtype, int64_t k);
-/* x: [K, rows] F32 contiguous (device) -> out: rows x GGUF-layout block_q8_0 / block_q8_K (device).
- * Bit-exact with quantize_row_q8_0 (AVX2 branch) / quantize_row_q8_K. */
+/* x: [K, rows] F32 contiguous (device) -> out: rows x GGUF-layout block_q8_0 / block_q8_K (device), or (vdt PS_F16) rows x K fp16.
+ * Bit-exact with quantize_row_q8_0 (AVX2 branch) / quantize_row_q8_K / ggml_fp32_to_fp16_row (F16C). */
 int ps_hip_quantize_act(ps_hip_ctx *ctx, int vdt, const float *x, int64_t K, int64_t rows, void *out_blocks);
 /* dst[ne01, ne11, ne12] = src0 x src1.  src0: quantized weight handle (2-D) or F32 tensor with arbitrary
  * nb[1..3] (K/V-cache views, GQA broadcast over dim 2); src1: F32, nb[0]==4; dst: F32 contiguous rows. */
@@ -141,7 +142,8 @@ int ps_hip_soft_max(ps_hip_ctx *ctx, const ps_tensor *dst, const ps_tensor *src)
 int ps_hip_add(ps_hip_ctx *ctx, const ps_tensor *dst, const ps_tensor *a, const ps_tensor *b);
 int ps_hip_dup(ps_hip_ctx *ctx, const ps_tensor *dst, const ps_tensor *src); /* COPY and CONT */
 int ps_hip_silu_hadamard(ps_hip_ctx *ctx, const ps_tensor *dst, const ps_tensor *gate, const ps_tensor *up);
-/* weight->data: ps_weight handle (quantized or F32 table [dim, vocab]); tokens: HOST int32[n] */
+/* weight->data: ps_weight handle (quantized, F32 or F16 table [dim, vocab]); tokens: HOST int32[n].  F16 rows are widened exactly -- beyond the
+ * reference, whose GGMLBackend::get_embedding asserts on FP16 tables (ggml_wrapper.cpp:193-206); a tied F16 lm_head needs it. */
 int ps_hip_get_embedding(ps_hip_ctx *ctx, const ps_tensor *dst, const ps_tensor *weight, const int32_t *tokens,
                          int n);
 /* dst [n_kv, bs] F32: (j <= pos[i]) ? 0 : -inf  — or, with tree != NULL (bs x bs bytes, row i = which batch
@@ -263,7 +265,7 @@ int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_wo
  * kv_advance); key 6: column blocks per XCD of the wide Q4_K / Q5_K mat-mul's item order (k_gemm4k.hip g4k_item: 0 = round 2's order, default 4;
  * PS_G4K_CBX); key 7: 1 = the fused Q / K / V + attention launch (k_qkvattn.hip) wherever it is covered -- by default only where its grid fills three quarters
  * of the chip (head size 128 with 8 kv heads), the head-size-64 instance otherwise runs under test only; key 9: the single-token attention kernels read the cached K rows / V channels
- * with plain (0) or non-temporal (1) loads whatever the cache's size, -1 (default): by the rule of csrc/model.hip (a cache-policy hint: no result bit depends on it; PS_KV_STREAM).
+ * with plain (0) or non-temporal (1) loads whatever the cache's size, -1 (default): by the rule of csrc/model.hip (a cache-policy hint: no result bit depends on it; PS_KV_STREAM); key 10: F16 batches on the matrix cores (0, default) or on the VALU chain kernel (1: A/B only, same bits).
  * Returns non-zero for an unknown key.  (A captured single-token step keeps the launch plan it was captured with: ps_hip_model_set_mode drops it.) */
 int ps_hip_debug_set(int key, int value);
 /* Diagnostic: one GEMM shape of the fp16 perf mode on synthetic operands (tools/f16_gemm_bench.py): out[M][N] = x[M][K] . W[N][K]^T, timed over

@@ -217,14 +217,14 @@ int ps_hip_vec_dot_type(int t) {
     case PS_Q4_0: case PS_Q8_0: return PS_Q8_0;
     case PS_Q4_K: case PS_Q5_K: case PS_Q6_K: return PS_Q8_K;
     }
-    return t;
+    return t; // F16: F16 (ggml.c:722-733), F32: F32
 }
 
 // ------------------------------------------------------------------ weights
 int ps_hip_weight_upload(ps_hip_ctx *c, int dtype, const void *host, int64_t K, int64_t N, ps_weight **out) {
     *out = nullptr;
-    if (!(is_quant(dtype) || dtype == PS_F32)) PS_FAIL(c, "weight_upload: unsupported dtype");
-    const int64_t blk = (dtype == PS_Q4_K || dtype == PS_Q5_K || dtype == PS_Q6_K) ? 256 : (dtype == PS_F32 ? 1 : 32);
+    if (!(is_quant(dtype) || dtype == PS_F32 || dtype == PS_F16)) PS_FAIL(c, "weight_upload: unsupported dtype");
+    const int64_t blk = (dtype == PS_Q4_K || dtype == PS_Q5_K || dtype == PS_Q6_K) ? 256 : ((dtype == PS_F32 || dtype == PS_F16) ? 1 : 32);
     if (K % blk) PS_FAIL(c, "weight_upload: K is not a multiple of the block size");
     if (PS_CONTRACT_ON && dtype == PS_Q5_K) PS_FAIL(c, "weight_upload: this is the PS_CONTRACT build (the reference's stock -ffp-contract=fast build); Q5_K's fused summs is not implemented in it");
     PS_CHECK(c, hipSetDevice(c->device));
@@ -235,7 +235,7 @@ int ps_hip_weight_upload(ps_hip_ctx *c, int dtype, const void *host, int64_t K, 
     w->gguf_bytes = (uint64_t)N * ps_hip_row_size(dtype, K);
     const size_t raw = (size_t)w->gguf_bytes;
     auto fail = [&](const char *m) { ps_hip_weight_free(c, w); c->err = m; return 1; };
-    if (dtype == PS_F32) {
+    if (dtype == PS_F32 || dtype == PS_F16) { // stored as the GGUF rows are (F16: k_gemvh.hip)
         if (ps_dev_malloc((void **)&w->qs, raw) != hipSuccess) return fail("weight_upload: hipMalloc");
         if (hipMemcpyAsync(w->qs, host, raw, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail("weight_upload: copy");
         PS_CHECK(c, hipStreamSynchronize(c->stream));
@@ -297,7 +297,12 @@ static int stage_i32(ps_hip_ctx *c, const int32_t *host, int n, int32_t **dev) {
 
 // ------------------------------------------------------------------ ops
 int ps_hip_quantize_act(ps_hip_ctx *c, int vdt, const float *x, int64_t K, int64_t rows, void *out_blocks) {
-    if (vdt != PS_Q8_0 && vdt != PS_Q8_K) PS_FAIL(c, "quantize_act: vdt must be Q8_0 or Q8_K");
+    if (vdt == PS_F16) { // ggml_fp32_to_fp16_row: out_blocks = rows x K fp16
+        psk_f16_act(c->stream, 0, x, nullptr, 0.f, K, rows, (_Float16 *)out_blocks);
+        PS_CHECK(c, hipGetLastError());
+        return 0;
+    }
+    if (vdt != PS_Q8_0 && vdt != PS_Q8_K) PS_FAIL(c, "quantize_act: vdt must be Q8_0, Q8_K or F16");
     if (K % (vdt == PS_Q8_0 ? 32 : 256)) PS_FAIL(c, "quantize_act: K not a multiple of the block size");
     if (ensure(c, &c->act_buf, &c->act_cap, ps_act_bytes(K, rows))) return 1;
     ps_act a = ps_act_carve(c->act_buf, K, rows);
@@ -352,6 +357,20 @@ int ps_hip_mul_mat(ps_hip_ctx *c, const ps_tensor *dst, const ps_tensor *src0, c
             g.pro = 2; g.pro_x = (const float *)src1->data + c0 * K;
             if (int rc = psk_gemv(c->stream, c->n_cu, g, a, vdt, K, nb)) { c->err = "mul_mat: gemv launch rc=" + std::to_string(rc); return 2; }
         }
+    } else if (src0->dtype == PS_F16) {
+        // any K: activation rounded to fp16 once, then the 32 fp32 chains + double leftovers of ggml_vec_dot_f16 (k_gemvh.hip)
+        const ps_weight *w = (const ps_weight *)src0->data;
+        if (!w || w->dtype != PS_F16 || w->K != src0->ne[0] || w->N != src0->ne[1]) PS_FAIL(c, "mul_mat: weight handle mismatch");
+        const int64_t K = w->K, bs = src1->ne[1] * src1->ne[2] * src1->ne[3];
+        if (src1->ne[0] != K || dst->ne[0] != w->N || dst->ne[1] * dst->ne[2] * dst->ne[3] != bs) PS_FAIL(c, "mul_mat: F16 shapes disagree with the weight");
+        if (src1->nb[1] != (uint64_t)K * 4 || dst->nb[1] != (uint64_t)w->N * 4) PS_FAIL(c, "mul_mat: F16 path needs contiguous rows");
+        if (src1->ne[2] > 1 && src1->nb[2] != src1->nb[1] * (uint64_t)src1->ne[1]) PS_FAIL(c, "mul_mat: F16 path needs contiguous rows");
+        if (dst->ne[2] > 1 && dst->nb[2] != dst->nb[1] * (uint64_t)dst->ne[1]) PS_FAIL(c, "mul_mat: F16 path needs contiguous rows");
+        if (ensure(c, &c->act_buf, &c->act_cap, (size_t)K * bs * 2 + 64)) return 1;
+        psk_gemv_args g{};
+        g.n_w = 1; g.w[0] = w; g.out[0] = (float *)dst->data; g.ldo[0] = w->N;
+        g.pro = 2; g.pro_x = (const float *)src1->data; // rounded in the launch's prologue (one column) or into act_buf first
+        if (int rc = psk_gemvh(c->stream, c->n_cu, g, (_Float16 *)c->act_buf, K, bs)) { c->err = "mul_mat: F16 launch rc=" + std::to_string(rc); return 2; }
     } else if (src0->dtype == PS_F32) {
         if (src0->nb[0] != 4) PS_FAIL(c, "mul_mat: transposed src0 not supported");
         if (src1->ne[2] % src0->ne[2] || src1->ne[3] % src0->ne[3]) PS_FAIL(c, "mul_mat: src0 not broadcastable");
@@ -474,7 +493,7 @@ int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_wo
 }
 
 int ps_hip_debug_set(int key, int value) {
-    extern int g_g4_cfg, g_g4_flags, g_g4k_par, g_f16_variant, g_force_attn_timeout, g_g4k_cbx, g_qa_force, g_kv_stream_force;
+    extern int g_g4_cfg, g_g4_flags, g_g4k_par, g_f16_variant, g_force_attn_timeout, g_g4k_cbx, g_qa_force, g_kv_stream_force, g_f16_batch;
     if (key == 1) { g_g4_cfg = value; return 0; }
     if (key == 2) { g_g4_flags = value; return 0; }
     if (key == 3) { g_g4k_par = value; return 0; }
@@ -482,6 +501,7 @@ int ps_hip_debug_set(int key, int value) {
     if (key == 5) { g_force_attn_timeout = value; return 0; }
     if (key == 6) { g_g4k_cbx = value; return 0; }
     if (key == 7) { g_qa_force = value; return 0; }
+    if (key == 10) { g_f16_batch = value; return 0; } // F16 batches: 0 matrix cores (default), 1 VALU chains (A/B)
     if (key == 9) { g_kv_stream_force = value; return 0; } // single-token attention: the cached K / V with plain (0) / non-temporal (1) loads whatever the cache's size; -1: by size (model.hip) // the fused QKV + attention launch wherever it is covered (default: only where its grid fills 3/4 of the chip)
     return 1;
 }

@@ -191,6 +191,8 @@ __global__ void get_rows_kernel(WView w, const int32_t *tokens, int n, float *ou
         float v;
         if (w.dtype == PS_F32) {
             v = ((const float *)w.qs)[row * K + e];
+        } else if (w.dtype == PS_F16) {
+            v = (float)((const _Float16 *)w.qs)[row * K + e]; // exact
         } else if (w.dtype == PS_Q4_0) {
             const int64_t nu = (K + 127) / 128, g = row / 16, blk = e / 32;
             const int r = (int)(row % 16), j = (int)(e % 32), byte = j & 15, bl = (int)(blk & 3);

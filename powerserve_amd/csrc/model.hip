@@ -81,6 +81,7 @@ struct ps_hip_model {
     psf16 *pf = nullptr;                // fp16 prefill perf mode (mode bit 5): fp16 copies of the layer matrices, fp16 activation scratch
     std::vector<_Float16 *> hq, hk, hv, ho, hg, hu, hd;
     _Float16 *xh = nullptr;
+    _Float16 *h16 = nullptr;            // [max_batch][max(dim, hidden)] fp16-rounded activation columns of the F16 mat-muls (k_gemvh.hip); only with F16 weights
     ps_step_state *state_sub = nullptr; // [64] per-chunk states of a super-chunk prefill (ps_hip_model_prefill)
     int attn_chunk = 0;                 // > 0 while such a forward is enqueued: the attention runs chunk by chunk
     hipGraphExec_t step_graph = nullptr;
@@ -127,6 +128,15 @@ static int mm_each(ps_hip_model *m, psk_gemv_args &g, ps_act act, int64_t K, int
         return 0;
     }
     for (int i = 0; i < g.n_w; i++) {
+        if (g.w[i]->dtype == PS_F16) { // one matrix of a mixed group: its own launch, the group's epilogue parts as mm_each gives them to every type
+            if (!g.pro || g.rope) { c->err = "F16 mat-mul: needs the fp32 activation and takes no fused RoPE"; return 2; }
+            psk_gemv_args s{};
+            s.n_w = 1; s.w[0] = g.w[i]; s.out[0] = g.silu_pair ? tmp[i] : g.out[i]; s.bias[0] = g.bias[i];
+            s.ldo[0] = g.ldo[i]; s.residual = (i == 0 && !g.silu_pair) ? g.residual : nullptr;
+            s.pro = g.pro; s.pro_x = g.pro_x; s.pro_norm_w = g.pro_norm_w; s.pro_eps = g.pro_eps; // (its own rounding, in its prologue for one column)
+            if (int rc = psk_gemvh(c->stream, c->n_cu, s, m->h16, K, bs)) { c->err = "F16 mat-mul launch rc=" + std::to_string(rc); return 2; }
+            continue;
+        }
         psk_gemv_args s{};
         s.n_w = 1; s.w[0] = g.w[i]; s.out[0] = g.silu_pair ? tmp[i] : g.out[i]; s.bias[0] = g.bias[i];
         s.ldo[0] = g.ldo[i]; s.residual = (i == 0 && !g.silu_pair) ? g.residual : nullptr;
@@ -163,6 +173,14 @@ static int mm_each(ps_hip_model *m, psk_gemv_args &g, ps_act act, int64_t K, int
 
 static int mm(ps_hip_model *m, psk_gemv_args &g, ps_act act, int64_t K, int64_t bs) {
     ps_hip_ctx *c = m->ctx;
+    bool any16 = false, all16 = true;
+    for (int i = 0; i < g.n_w; i++) { any16 = any16 || g.w[i]->dtype == PS_F16; all16 = all16 && g.w[i]->dtype == PS_F16; }
+    if (all16) { // F16 group: ONE launch for all matrices, the activation (with its RMSNorm) rounded to fp16 in its prologue (one column) or once before it
+        if (!g.pro || g.rope) { c->err = "F16 mat-mul: needs the fp32 activation and takes no fused RoPE"; return 2; }
+        if (int rc = psk_gemvh(c->stream, c->n_cu, g, m->h16, K, bs)) { c->err = "F16 mat-mul launch rc=" + std::to_string(rc); return 2; }
+        return 0;
+    }
+    if (any16) return mm_each(m, g, act, K, bs);
     if (bs == 1 && (g.w[0]->dtype == PS_Q6_K || g.w[0]->dtype == PS_Q5_K)) { // single token: the launch with its fused prologue / epilogue (k_gemvk.hip)
         const int rc = psk_gemvk(c->stream, c->n_cu, g, act, K); // (-1: mixed types, a pair it does not take, ...)
         if (rc == 0) return 0;
@@ -219,6 +237,7 @@ static int ensure_perf16(ps_hip_model *m) {
     if (cap > m->max_batch) cap = m->max_batch;
     if (cap < 1) { psf16_destroy(pf); PS_FAIL(c, "fp16 perf mode: no scratch for the dequantizer"); }
     auto copy = [&](const ps_weight *w, std::vector<_Float16 *> &dst) -> int {
+        if (w->dtype == PS_F16) { dst.push_back((_Float16 *)w->qs); return 0; } // already the [N][K] fp16 matrix: no second copy
         _Float16 *h = nullptr;
         if (dmalloc(m, (void **)&h, (size_t)w->N * w->K * 2)) return 2;
         dst.push_back(h);
@@ -230,7 +249,8 @@ static int ensure_perf16(ps_hip_model *m) {
         for (auto *v : {&m->hq, &m->hk, &m->hv, &m->ho, &m->hg, &m->hu, &m->hd}) {
             for (_Float16 *h : *v) {
                 auto it = std::find(m->owned.begin(), m->owned.end(), (void *)h);
-                if (it != m->owned.end()) m->owned.erase(it);
+                if (it == m->owned.end()) continue; // an F16 weight's own matrix
+                m->owned.erase(it);
                 (void)ps_dev_free(h);
             }
             v->clear();
@@ -400,7 +420,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
         }
         if (mm(m, go, a1, dim, bs)) return 2;
         if (mm(m, gf, a1, dim, bs)) return 2;
-        if (psk_gemv_lds_col_bytes(m->wd[L]->dtype, hid) * (bs == 1 ? 1 : 4) <= 64 * 1024 && (hid <= 8192 || bs == 1)) {
+        if (m->wd[L]->dtype == PS_F16 || (psk_gemv_lds_col_bytes(m->wd[L]->dtype, hid) * (bs == 1 ? 1 : 4) <= 64 * 1024 && (hid <= 8192 || bs == 1))) {
             gd.pro = 2; gd.pro_x = m->hb; // short rows: quantize in the prologue
         } else {
             psk_quantize_act(st, vdt_d, 0, m->hb, nullptr, nullptr, 0.f, hid, bs, a2);
@@ -432,11 +452,11 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
         PS_FAIL(c, "model_create: inconsistent head configuration");
     { // the descriptor is trusted by every kernel: weight handles must exist and agree with the configuration
         auto okw = [](const ps_weight *w, int64_t K, int64_t N) {
-            return w && w->K == K && w->N == N && w->qs && (w->dtype == PS_Q4_0 || w->dtype == PS_Q8_0 || w->dtype == PS_Q4_K || w->dtype == PS_Q5_K || w->dtype == PS_Q6_K);
+            return w && w->K == K && w->N == N && w->qs && (w->dtype == PS_Q4_0 || w->dtype == PS_Q8_0 || w->dtype == PS_Q4_K || w->dtype == PS_Q5_K || w->dtype == PS_Q6_K || w->dtype == PS_F16);
         };
         if (!d->token_embd || d->token_embd->K != f.dim || d->token_embd->N != f.vocab_size || !d->token_embd->qs) PS_FAIL(c, "model_create: token_embd missing or of the wrong shape");
         if (d->output && !okw(d->output, f.dim, f.vocab_size)) PS_FAIL(c, "model_create: output.weight of the wrong shape / type");
-        if (!d->output && !okw(d->token_embd, f.dim, f.vocab_size)) PS_FAIL(c, "model_create: tied lm_head needs a quantized token_embd");
+        if (!d->output && !okw(d->token_embd, f.dim, f.vocab_size)) PS_FAIL(c, "model_create: tied lm_head needs a quantized or F16 token_embd");
         if (!d->output_norm || !d->attn_norm || !d->ffn_norm || !d->attn_q || !d->attn_k || !d->attn_v || !d->attn_output || !d->ffn_gate || !d->ffn_up || !d->ffn_down)
             PS_FAIL(c, "model_create: null weight table");
         for (uint32_t i = 0; i < f.n_layers; i++) {
@@ -486,6 +506,12 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
         dmalloc(m, (void **)&m->argmax_dev, mb * 4) || dmalloc(m, (void **)&m->ids_dev, (nctx + 1) * 4) ||
         dmalloc(m, (void **)&m->tree_dev, mb * mb) || dmalloc(m, (void **)&m->rope_pos_dev, mb * 4) || dmalloc(m, (void **)&m->kv_vis_dev, nctx) || dmalloc(m, (void **)&m->am_v, mb * 64 * 4) || dmalloc(m, (void **)&m->am_i, mb * 64 * 4))
         return fail();
+    {
+        bool any16 = (m->output ? m->output : m->token_embd)->dtype == PS_F16;
+        for (uint32_t i = 0; i < L; i++)
+            for (const ps_weight *w : {m->wq[i], m->wk[i], m->wv[i], m->wo[i], m->wg[i], m->wu[i], m->wd[i]}) any16 = any16 || w->dtype == PS_F16;
+        if (any16 && dmalloc(m, (void **)&m->h16, mb * (dim > hid ? dim : hid) * 2)) return fail();
+    }
     (void)hipMemsetAsync(m->attn_sync, 0, 2048 * 4, c->stream);
     if (hipHostMalloc((void **)&m->attn_flag_host, 64, hipHostMallocDefault) != hipSuccess) return fail();
     *m->attn_flag_host = 0;

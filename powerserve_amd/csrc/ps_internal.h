@@ -48,6 +48,7 @@ struct ps_hip_ctx {
 //          element e of sub-vector 2 jj in the low nibble, of 2 jj + 1 in the high one)   qh [N][K/256][u][4 B] = qh bytes 4u..
 //          (bit b = fifth bit of sub-vector b)   sc [N][K/256] 16 B = {d, dmin, scales[12]}
 //   F32  : qs [N][K] float
+//   F16  : qs [N][K] fp16, the GGUF rows as they are (k_gemvh.hip)
 struct ps_weight {
     int dtype;
     int64_t K, N;
@@ -192,6 +193,12 @@ int psk_gemv6(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int
 int psk_gemv5_multi(hipStream_t st, int n_cu, const psk_gemv6_args *a, int n_w, ps_act act, int64_t K, int64_t bs); // up to 3 Q5_K matrices, one launch
 int psk_gemm5k(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int64_t K, int64_t bs); // Q5_K batches (k_gemm4k.hip); -1: not covered
 int psk_gemm6k(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int64_t K, int64_t bs); // Q6_K, >= 17 columns (k_gemm4k.hip); -1: not covered
+// F16 weights (k_gemvh.hip): activation rows -> fp16 rows bit-equal to ggml_fp32_to_fp16_row (mode 1: RMSNorm(x, norm_w, eps) first), and the
+// mat-vec / mat-mul on them (psk_gemv_args without `rope`).  pro 1 / 2: the fp32 column(s) pro_x are rounded (pro 1: after the RMSNorm) in
+// the launch's prologue (one column) or by psk_f16_act into x16 ([bs][K] fp16 scratch) first; pro 0: x16 holds the rounded columns.
+// Batches with K % 8 == 0 run on the matrix cores.  Non-zero: not covered.
+void psk_f16_act(hipStream_t st, int mode, const float *x, const float *norm_w, float eps, int64_t K, int64_t rows, _Float16 *out);
+int psk_gemvh(hipStream_t st, int n_cu, const psk_gemv_args &a, _Float16 *x16, int64_t K, int64_t bs);
 int psk_gemv_debug(int key, uint64_t *host_out, int n_words); // timeline buffer: arm / read back
 int psk_gemv(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int vdt, int64_t K, int64_t bs);
 // second-generation single-column Q4_K mat-vec (k_gemv4.hip); -1: not covered, the caller falls back

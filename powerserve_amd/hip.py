@@ -248,7 +248,7 @@ class Weight:
 
     def tensor(self) -> PSTensor:
         rs = self.ctx.L.ps_hip_row_size(self.dtype, self.K)
-        ts = {F32: 4, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210}[self.dtype]
+        ts = {F32: 4, F16: 2, Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210}[self.dtype]
         return PSTensor(self.dtype, 0, (C.c_int64 * 4)(self.K, self.N, 1, 1), (C.c_uint64 * 4)(ts, rs, rs * self.N, rs * self.N),
                         self.h)
 

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import gguf
-from .gguf import F32, Q4_0, Q4_K, Q5_K, Q6_K, Q8_0
+from .gguf import F16, F32, Q4_0, Q4_K, Q5_K, Q6_K, Q8_0
 
 # SURVEY.md §8 shape table (public HF configs)
 PRESETS = {
@@ -72,6 +72,8 @@ def random_blocks(rng: np.random.Generator, t: int, n_rows: int, k: int, std: fl
     """Random valid GGUF blocks for an [k, n_rows] weight; returns uint8 [n_rows * row_size]."""
     if t == F32:
         return (rng.standard_normal((n_rows, k), dtype=np.float32) * std).view(np.uint8).reshape(-1)
+    if t == F16:  # the unquantized export (convert_hf_to_gguf): fp16 rows
+        return _f16(rng.standard_normal((n_rows, k), dtype=np.float32) * std).view(np.uint8).reshape(-1)
     blk, ts = gguf.BLOCK[t]
     nb = n_rows * (k // blk)
     out = np.empty((nb, ts), dtype=np.uint8)
@@ -114,6 +116,7 @@ def random_blocks(rng: np.random.Generator, t: int, n_rows: int, k: int, std: fl
 
 
 Q5_K_M = 1017  # pseudo type: llama.cpp's "Q5_K_M" recipe, Q5_K with Q6_K for the same sensitive tensors
+F16_Q8_0 = 1001  # pseudo type: F16 attention matrices (and output / token_embd) next to Q8_0 FFN matrices
 Q4_K_M = 1015  # pseudo type: the per-tensor mix llama.cpp's "Q4_K_M" file type uses (Q4_K with Q6_K for the sensitive tensors)
 
 
@@ -124,6 +127,9 @@ def _more_bits(i: int, n: int) -> bool:  # llama.cpp use_more_bits(i_layer, n_la
 def tensor_plan(cfg: dict, arch: str, wtype: int, tied: bool, embd_type: int | None = None):
     """[(name, type, ne)] in file order."""
     dim, hid, L, kvd, vocab = cfg["embed_dim"], cfg["ffn_dim"], cfg["n_layers"], cfg["kv_dim"], cfg["vocab_size"]
+    if wtype == F16_Q8_0:
+        plan = tensor_plan(cfg, arch, F16, tied, embd_type)
+        return [(n, Q8_0 if ".ffn_" in n and n.endswith("weight") and t == F16 else t, ne) for n, t, ne in plan]
     mix = wtype in (Q4_K_M, Q5_K_M)
     if mix:
         wtype = Q4_K if wtype == Q4_K_M else Q5_K
@@ -156,7 +162,7 @@ def write_model_dir(out_dir: str, preset: str, wtype: int, n_ctx: int, seed: int
     tied = PRESETS[preset][10]
     cfg = llm_config(preset, n_ctx, rope_freq_scale, rope_attn_factor)
     os.makedirs(os.path.join(out_dir, "ggml"), exist_ok=True)
-    mj = {"version": 1, "model_arch": arch, "model_id": model_id or f"{preset}-{'Q4_K_M' if wtype == Q4_K_M else ('Q5_K_M' if wtype == Q5_K_M else gguf.TYPE_NAME[wtype])}",
+    mj = {"version": 1, "model_arch": arch, "model_id": model_id or f"{preset}-{'Q4_K_M' if wtype == Q4_K_M else ('Q5_K_M' if wtype == Q5_K_M else ('F16_Q8_0' if wtype == F16_Q8_0 else gguf.TYPE_NAME[wtype]))}",
           "llm_config": cfg}
     with open(os.path.join(out_dir, "model.json"), "w") as f:
         json.dump(mj, f, indent=1)
