@@ -256,6 +256,11 @@ int ps_hip_model_bench_matmul(ps_hip_model *m, int reps, int which, int bs, doub
  * the same size (kernel-boundary gaps). */
 /* diagnostics: the kernel (rocprofv3's template name) the most recent quantized mat-mul launch of this process went to */
 const char *ps_hip_last_matmul_kernel(void);
+/* diagnostics: the single-token attention the most recent single-token forward of this process enqueued (rocprofv3's template name):
+ * "qkv_attn_kernel<NV, KVS>" (fused with the Q / K / V mat-vec), "attn_decode2_kernel<NV, NT, KVS>" (one launch), "attn_scores_kernel<NV> + attn_softmax_pv_kernel"
+ * (two launches, mode bit 4) or "attn_flash16_kernel<HS>" (fp16-KV decode mode, bit 3); "" before any.  Noted at enqueue time: after a captured step's
+ * replay it names what the capture enqueued. */
+const char *ps_hip_last_attention_kernel(void);
 int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_words);
 /* Diagnostic: tunables of the library (process-wide).  key 1: wave configuration of the decode mat-vec (k_gemv4.hip,
  * tools/g4_variants.py); key 3: the narrow-batch Q4_K mat-mul for few row tiles (k_gemm4k.hip: 0 = gemm4k_par_kernel off (the wave-per-tile / staged forms take the launch: A/B only),

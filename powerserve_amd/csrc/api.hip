@@ -482,8 +482,16 @@ void psk_note_kernel(const char *fmt, ...) {
     va_end(ap);
 }
 const char *psk_last_kernel() { return g_last_kernel; }
+static char g_last_attn[128] = "";
+void psk_note_attn(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_last_attn, sizeof(g_last_attn), fmt, ap);
+    va_end(ap);
+}
 extern "C" {
 const char *ps_hip_last_matmul_kernel(void) { return psk_last_kernel(); }
+const char *ps_hip_last_attention_kernel(void) { return g_last_attn; }
 int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_words) {
     if (!ctx) return 1;
     if (!PS_TIMELINE && key >= 0) PS_FAIL(ctx, "debug_timeline: this library is built without the in-kernel timeline marks (they cost the decode path 3 %); "
@@ -500,9 +508,9 @@ int ps_hip_debug_set(int key, int value) {
     if (key == 4) { g_f16_variant = value; return 0; }
     if (key == 5) { g_force_attn_timeout = value; return 0; }
     if (key == 6) { g_g4k_cbx = value; return 0; }
-    if (key == 7) { g_qa_force = value; return 0; }
+    if (key == 7) { g_qa_force = value; return 0; } // the fused QKV + attention launch wherever it is covered (default: only where its grid fills 3/4 of the chip)
     if (key == 10) { g_f16_batch = value; return 0; } // F16 batches: 0 matrix cores (default), 1 VALU chains (A/B)
-    if (key == 9) { g_kv_stream_force = value; return 0; } // single-token attention: the cached K / V with plain (0) / non-temporal (1) loads whatever the cache's size; -1: by size (model.hip) // the fused QKV + attention launch wherever it is covered (default: only where its grid fills 3/4 of the chip)
+    if (key == 9) { g_kv_stream_force = value; return 0; } // single-token attention: the cached K / V with plain (0) / non-temporal (1) loads whatever the cache's size; -1: by size (model.hip)
     return 1;
 }
 

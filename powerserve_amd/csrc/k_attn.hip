@@ -1396,6 +1396,7 @@ void psl_attn_softmax_pv(hipStream_t st, const psl_attn_args &a, int bs) {
     static unsigned long long attr = 0; // devices that have the attribute
     if (ps_first_on_device(&attr)) { (void)hipFuncSetAttribute((const void *)attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); }
     dim3 g((unsigned)(a.head_size / 4), (unsigned)a.n_kv_heads, (unsigned)bs);
+    psk_note_attn("attn_scores_kernel<%d> + attn_softmax_pv_kernel", a.head_size / 32); // (bs == 1: psl_attn_scores took attn_scores_kernel)
     hipLaunchKernelGGL(attn_softmax_pv_kernel, g, dim3(PV_NT), psl_attn_softmax_pv_lds(a), st, a);
 }
 
@@ -1404,6 +1405,7 @@ bool psl_attn_decode_f16(hipStream_t st, const psl_attn_args &a) {
     const int r2 = a.n_heads / a.n_kv_heads;
     if ((r2 != 1 && r2 != 2 && r2 != 4 && r2 != 8) || (a.head_size != 128 && a.head_size != 64)) return false;
     const dim3 g(FL_SPLITS, (unsigned)a.n_kv_heads);
+    psk_note_attn("attn_flash16_kernel<%d>", a.head_size);
     if (a.head_size == 128) hipLaunchKernelGGL(attn_flash16_kernel<128>, g, dim3(FL_NT), 0, st, a);
     else hipLaunchKernelGGL(attn_flash16_kernel<64>, g, dim3(FL_NT), 0, st, a);
     return true;
@@ -1429,6 +1431,7 @@ bool psl_attn_decode2(hipStream_t st, int n_cu, const psl_attn_args &a) {
     // slower in total (14.05 vs 13.66 us: twice the soft-max numerators per lane, issue-bound); with ps_v_expf_n they win: 8B decode 534.9 -> 542.8 tok/s
     // (profiles/r04_gemv_variants.txt).  PS_ATTN_NT=1024 brings the round-3 geometry back for an A/B run.
     static const int nt_env = getenv("PS_ATTN_NT") ? atoi(getenv("PS_ATTN_NT")) : 512;
+    psk_note_attn("attn_decode2_kernel<%d, %d, %d>", a.head_size / 32, nt_env == 512 ? 512 : 1024, a.kv_stream ? 1 : 0);
     static unsigned long long attr5 = 0;
     if (ps_first_on_device(&attr5)) {
         (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<4, 512, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);

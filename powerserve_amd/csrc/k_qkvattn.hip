@@ -623,6 +623,18 @@ bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, c
     if (!a.xchg || !a.tick || !a.sync || a.tree || a.rope_pos || a.neox || a.k16 || a.v16 || r2 > 4 || a.n_ctx > QA_MAXCTX || a.n_dims > hs) return false;
     if (g.w[0]->N != (int64_t)a.n_heads * hs || g.w[1]->N != (int64_t)a.n_kv_heads * hs || g.w[2]->N != g.w[1]->N) return false;
     if (G * a.n_kv_heads > n_cu) return false; // every workgroup resident (one per CU: the LDS)
+    // Visibility precondition (see the head of this file): before rendezvous A a workgroup pulls the columns [0, pos0 & ~31) of its four V rows, and that is a
+    // set of whole 128-byte lines below the new column's line only when every row starts on a line -- V is [kv_dim][n_ctx], so row r starts r * n_ctx * 4 bytes
+    // into the layer's cache.  With n_ctx % 32 != 0 the pull of a row r >= 1 can take the very line that holds V[pos0], which another workgroup's chain wave
+    // writes in this launch: a stale copy of it in the reader's L1 then meets the plain load after the rendezvous.  Such shapes take the two launches.
+    if (a.n_ctx % 32) return false;
+    auto line = [](const void *ptr) { return ((uintptr_t)ptr & 127) == 0; };
+    if (!line(a.v_cache) || !line(a.k_cache) || !line(a.q) || !line(a.xchg)) return false;
+    // the mat-vec half writes what the attention half reads: one q, one cache, one rotation
+    const psk_rope_kv &rk = *g.rope;
+    if (g.out[0] != a.q || rk.rope_table != a.rope_table || rk.rope_pos || rk.k_cache != a.k_cache || rk.v_cache != a.v_cache || rk.head_size != hs ||
+        rk.n_dims != a.n_dims || rk.n_ctx != a.n_ctx || rk.kv_dim != a.n_kv_heads * hs || rk.state != a.state || rk.k16 || rk.v16) return false;
+    if (!psk_gemv4_covers(K)) return false; // (PS_NO_GEMV4 switches the mat-vec half off with the mat-vec it restates)
     // The launch has head_size / 4 workgroups per kv head: 256 for Llama-3.1-8B's shape, 128 for Llama-3.2-1B's (head size 64) -- half the chip for a mat-vec that the
     // unfused launch spreads over every CU: measured slower there (tools/gpu_fused_stress.py, profiles/r06_fused_stress.txt: 11.9 k vs 12.4 k tok/s on the 2-layer
     // 1B shape in Q4_K, against 4.84 k vs 4.77 k on the 4-layer 8B shape).  Taken only where its grid fills at least three quarters of the chip;
@@ -650,6 +662,7 @@ bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, c
         (void)hipFuncSetAttribute((const void *)qkv_attn_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     const dim3 grid((unsigned)(G * a.n_kv_heads));
+    psk_note_attn("qkv_attn_kernel<%d, %d>", hs / 32, a.kv_stream ? 1 : 0);
     if (hs == 128) { if (a.kv_stream) hipLaunchKernelGGL((qkv_attn_kernel<4, 1>), grid, dim3(QA_THREADS), lds, st, p); else hipLaunchKernelGGL((qkv_attn_kernel<4, 0>), grid, dim3(QA_THREADS), lds, st, p); }
     else { if (a.kv_stream) hipLaunchKernelGGL((qkv_attn_kernel<2, 1>), grid, dim3(QA_THREADS), lds, st, p); else hipLaunchKernelGGL((qkv_attn_kernel<2, 0>), grid, dim3(QA_THREADS), lds, st, p); }
     return true;

@@ -215,3 +215,6 @@ unsigned long long *psk_gemv_dbg_buf(int epi, int pro); // timeline slot armed f
 // roofline names the kernel that RAN, not the one it expects
 void psk_note_kernel(const char *fmt, ...);
 const char *psk_last_kernel();
+// the same for the single-token attention (ps_hip_last_attention_kernel): which of the fused Q / K / V + attention launch, attn_decode2, the scores + soft-max.V.p
+// pair or attn_flash16 the last single-token forward enqueued -- noted at enqueue time, so a captured graph reports what it captured
+void psk_note_attn(const char *fmt, ...);

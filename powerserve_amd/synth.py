@@ -45,6 +45,8 @@ PRESETS = {
     "odd-llama-r5": ("llama", 320, 640, 2, 5, 1, 64, 512, 5e5, 0, False, 1e-5),
     "odd-llama-r6": ("llama", 768, 1024, 2, 6, 1, 128, 512, 5e5, 0, False, 1e-5),
     "odd-llama-r8": ("llama", 512, 1024, 2, 8, 1, 64, 512, 5e5, 0, True, 1e-5),
+    # one query head per kv head at head size 128 (odd-llama-hs32 has the ratio at a head size the single-token kernels do not take): tests/test_gpu_attn_ctx.py
+    "odd-llama-r1": ("llama", 512, 1024, 2, 4, 4, 128, 512, 5e5, 0, False, 1e-5),
 }
 
 

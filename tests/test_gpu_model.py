@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from attn_reference import attention_reference
 from conftest import load_tensors, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -115,34 +116,37 @@ def test_decode_attention_long_cache_matches_oracle(ctx, oracle, tmp_path, prese
     steps = 40
     want_ids, want_logits, *_ = om.generate(prompt, 128, steps, want_logits=True)
     assert ctx.L.ps_hip_debug_set(7, 1) == 0  # (the fused QKV + attention launch wherever it is covered: also its head-size-64 instance)
-    gm = hip.Model(ctx, d, max_batch=128, n_ctx=n_ctx)
-    assert np.array_equal(gm.generate(prompt, 128, steps), want_ids)           # hipGraph replay
-    gm.set_mode(1)
-    assert np.array_equal(gm.generate(prompt, 128, steps), want_ids)           # eager launches
-    gm.set_mode(0)
-    gm.kv_rollback(steps)                                                      # back to the end of the prompt
-    cur = int(prompt[-1])
-    for s in range(steps):                                                     # eager single-token forwards: exact host hint
-        lg, am = gm.forward([cur], [gm.position], lm_head=True)
-        assert np.array_equal(np.asarray(lg[0]).view(np.uint32), np.asarray(want_logits[s]).view(np.uint32)), s
-        cur = int(want_ids[s])
-    # hidden slots: the two attention plans agree bit for bit (and differ from the unmasked logits)
-    hidden = [3, 40, P // 2, P - 2]
-    outs = []
-    for mode in (0, 128, 16):  # the fused QKV + attention launch / its two launches (QKV mat-vec, attn_decode2) / scores + soft-max.V.p behind the QKV mat-vec
-        gm.set_mode(mode)
-        gm.kv_rollback(5)
-        for h in hidden:
-            gm.kv_mask(h, False)
-        res = []
-        for s in range(5):
-            lg, am = gm.forward([int(want_ids[steps - 6 + s])], [gm.position], lm_head=True)  # (teacher forcing: step k is fed id k - 1)
-            res.append(np.asarray(lg[0]).copy())
-        for h in hidden:
-            gm.kv_mask(h, True)
-        outs.append(np.stack(res))
-    assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32)) and np.array_equal(outs[0].view(np.uint32), outs[2].view(np.uint32))
-    assert not np.array_equal(outs[0][0], np.asarray(want_logits[steps - 5]))                     # (unmasked, these would be step steps - 5's logits)
+    try:
+        gm = hip.Model(ctx, d, max_batch=128, n_ctx=n_ctx)
+        assert np.array_equal(gm.generate(prompt, 128, steps), want_ids)           # hipGraph replay
+        gm.set_mode(1)
+        assert np.array_equal(gm.generate(prompt, 128, steps), want_ids)           # eager launches
+        gm.set_mode(0)
+        gm.kv_rollback(steps)                                                      # back to the end of the prompt
+        cur = int(prompt[-1])
+        for s in range(steps):                                                     # eager single-token forwards: exact host hint
+            lg, am = gm.forward([cur], [gm.position], lm_head=True)
+            assert np.array_equal(np.asarray(lg[0]).view(np.uint32), np.asarray(want_logits[s]).view(np.uint32)), s
+            cur = int(want_ids[s])
+        # hidden slots: the two attention plans agree bit for bit (and differ from the unmasked logits)
+        hidden = [3, 40, P // 2, P - 2]
+        outs = []
+        for mode in (0, 128, 16):  # the fused QKV + attention launch / its two launches (QKV mat-vec, attn_decode2) / scores + soft-max.V.p behind the QKV mat-vec
+            gm.set_mode(mode)
+            gm.kv_rollback(5)
+            for h in hidden:
+                gm.kv_mask(h, False)
+            res = []
+            for s in range(5):
+                lg, am = gm.forward([int(want_ids[steps - 6 + s])], [gm.position], lm_head=True)  # (teacher forcing: step k is fed id k - 1)
+                res.append(np.asarray(lg[0]).copy())
+            for h in hidden:
+                gm.kv_mask(h, True)
+            outs.append(np.stack(res))
+        assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32)) and np.array_equal(outs[0].view(np.uint32), outs[2].view(np.uint32))
+        assert not np.array_equal(outs[0][0], np.asarray(want_logits[steps - 5]))                     # (unmasked, these would be step steps - 5's logits)
+    finally:
+        ctx.L.ps_hip_debug_set(7, 0)
     assert ctx.L.ps_hip_debug_set(7, 0) == 0
     gm.close()
     om.close()
@@ -163,18 +167,21 @@ def test_fused_qkv_attention_from_an_empty_cache(ctx, oracle, tmp_path, preset):
     toks = np.random.default_rng(2).integers(0, cfg.vocab_size, 70)
     want = [om.forward([int(t)], [i], True)[0] for i, t in enumerate(toks)]
     assert ctx.L.ps_hip_debug_set(7, 1) == 0  # (the head-size-64 instance fills half the chip and is not dispatched by default: taken here wherever it is covered)
-    gm = hip.Model(ctx, d, max_batch=8, n_ctx=256)
-    for mode in (1, 129):  # eager: fused / two launches
-        gm.set_mode(mode)
+    try:
+        gm = hip.Model(ctx, d, max_batch=8, n_ctx=256)
+        for mode in (1, 129):  # eager: fused / two launches
+            gm.set_mode(mode)
+            gm.reset()
+            for i, t in enumerate(toks):
+                lg, _ = gm.forward([int(t)], [i], lm_head=True)
+                assert np.array_equal(np.asarray(lg[0]).view(np.uint32), np.asarray(want[i]).view(np.uint32)), (mode, i)
+        om.reset()
+        want_ids, *_ = om.generate(toks[:1], 8, 40)
+        gm.set_mode(0)
         gm.reset()
-        for i, t in enumerate(toks):
-            lg, _ = gm.forward([int(t)], [i], lm_head=True)
-            assert np.array_equal(np.asarray(lg[0]).view(np.uint32), np.asarray(want[i]).view(np.uint32)), (mode, i)
-    om.reset()
-    want_ids, *_ = om.generate(toks[:1], 8, 40)
-    gm.set_mode(0)
-    gm.reset()
-    assert np.array_equal(gm.generate(toks[:1], 8, 40), want_ids)  # hipGraph replay from position 0
+        assert np.array_equal(gm.generate(toks[:1], 8, 40), want_ids)  # hipGraph replay from position 0
+    finally:
+        ctx.L.ps_hip_debug_set(7, 0)
     assert ctx.L.ps_hip_debug_set(7, 0) == 0
     gm.close()
     om.close()
@@ -493,21 +500,6 @@ def test_kv_full_and_bad_tokens_fail_loudly(ctx, tmp_path):
     with pytest.raises(hip.PSHipError):
         gm.forward([1, 2], [0, 2], lm_head=False)                # non-consecutive positions
     gm.close()
-
-
-def attention_reference(m, n_kv):
-    """softmax(q K^T / sqrt(hs)) V of the LAST layer in float64 from the model's own q and FP32 caches"""
-    c = m.cfg
-    hs, r2 = c.head_size, c.n_heads // c.n_kv_heads
-    q = m.scratch(1, 1)[0].astype(np.float64).reshape(c.n_heads, hs)
-    K = m.k_cache(c.n_layers - 1)[:n_kv].astype(np.float64).reshape(n_kv, c.n_kv_heads, hs)
-    V = m.v_cache(c.n_layers - 1).astype(np.float64)[:, :n_kv].reshape(c.n_kv_heads, hs, n_kv)
-    out = np.empty((c.n_heads, hs))
-    for h in range(c.n_heads):
-        s = K[:, h // r2, :] @ q[h] / np.sqrt(hs)
-        p = np.exp(s - s.max()); p /= p.sum()
-        out[h] = V[h // r2] @ p
-    return out.reshape(-1)
 
 
 @pytest.mark.parametrize("preset,wt,n_prompt,n_ctx", [("small-llama-hs128", 12, 150, 256), ("tiny-llama", 8, 37, 256), ("small-llama", 2, 90, 256),

@@ -25,7 +25,7 @@ ap.add_argument("--ops-share", type=float, default=0.3)
 ap.add_argument("--max-draws", type=int, default=0, help="stop after this many draws (0: by --seconds only): a fixed, repeatable sequence")
 ap.add_argument("--big-ctx", action="store_true", help="context windows of 4608 / 6144 slots with caches longer than 4096 tokens (the two-launch single-token attention, the LDS-row soft-max)")
 ap.add_argument("--odd-share", type=float, default=0.0, help="share of model draws from the odd head-size / GQA-ratio presets")
-ap.add_argument("--replay", default="", help="one model draw instead of the sweep: 'preset wt n_ctx P chunk max_batch steps tree seed' (values of a draw line)")
+ap.add_argument("--replay", default="", help="one model draw instead of the sweep: 'preset wt n_ctx P chunk max_batch steps tree seed [qa_force]' (values of a draw line)")
 ap.add_argument("--verbose", action="store_true", help="print every draw before it runs (the last line names a draw that killed the process)")
 args = ap.parse_args()
 
@@ -90,7 +90,9 @@ def stage(name):
         print("  done:", name, flush=True)
 
 
-def model_case(tmp):
+def model_case(tmp, qa_force):
+    """qa_force: ps_hip_debug_set(7, 1) for this draw -- the fused Q / K / V + attention launch wherever psk_qkv_attn covers the shape, not only where its
+    grid fills three quarters of the chip (the presets here are too narrow for that), so that its cover decision sees the drawn context windows"""
     global n_models, n_trees, n_host
     pool = ODD if rng.random() < args.odd_share else MODELS
     preset, wts = pool[int(rng.integers(0, len(pool)))]
@@ -115,7 +117,7 @@ def model_case(tmp):
     if args.replay:
         f = args.replay.split()
         preset, (wt, n_ctx, P, chunk, max_batch, steps, n_tree, seed) = f[0], [int(v) for v in f[1:9]]
-    tag = f"{preset} wt={wt} n_ctx={n_ctx} P={P} chunk={chunk} max_batch={max_batch} steps={steps} tree={n_tree} seed={seed}"
+    tag = f"{preset} wt={wt} n_ctx={n_ctx} P={P} chunk={chunk} max_batch={max_batch} steps={steps} tree={n_tree} seed={seed} qa_force={qa_force}"
     if args.verbose:
         print("draw", tag, flush=True)
     d = os.path.join(tmp, f"m{n_models}")
@@ -198,18 +200,30 @@ def model_case(tmp):
                 pass
 
 
+def forced_model_case(tmp, qa_force):
+    """model_case with ps_hip_debug_set(7, qa_force) around it (--replay: the draw line's value)"""
+    if args.replay:
+        f = args.replay.split()
+        qa_force = int(f[9]) if len(f) > 9 else 0
+    assert ctx.L.ps_hip_debug_set(7, qa_force) == 0
+    try:
+        model_case(tmp, qa_force)
+    finally:
+        ctx.L.ps_hip_debug_set(7, 0)
+
+
 with tempfile.TemporaryDirectory() as tmp:
     n_draws = 0
     while time.time() < t_end and len(fails) < 10 and (args.max_draws <= 0 or n_draws < args.max_draws):
         n_draws += 1
         try:
             if args.replay:
-                model_case(tmp)
+                forced_model_case(tmp, 0)
                 break
             if rng.random() < args.ops_share:
                 op_case()
             else:
-                model_case(tmp)
+                forced_model_case(tmp, n_draws % 2)  # (keyed on the draw index, not drawn: the seeded sweeps keep their draws)
         except Exception as e:  # a refused shape is a finding too: report the draw, keep going
             fails.append(f"exception: {type(e).__name__}: {str(e)[:300]}")
 print(f"gpu_fuzz seed {args.seed}: {n_ops} mat-muls, {n_models} models (generate + per-step logits + cache rows), {n_trees} tree forwards, {n_host} runs of the reference-API path; {len(fails)} failures")
