@@ -229,6 +229,40 @@ int ps_hip_model_kv_mask(ps_hip_model *m, size_t index, int visible);
  * KV position, then its own arg-max, `steps` times, without host round trips (hipGraph replay).  out_ids
  * HOST int32[steps]. */
 int ps_hip_model_decode_greedy(ps_hip_model *m, int32_t token, int steps, int32_t *out_ids);
+
+/* ---- sampled decoding on the device: the standard sampler chain (repeat penalty / EOS ban -> top-k -> temperature -> soft-max ->
+ * top-p -> normalize -> std::mt19937 + std::discrete_distribution), token for token what the host SamplerChain (csrc/host/sampler.cpp)
+ * draws from the same logits, configuration and engine state (DESIGN.md "Sampled decode on the device").
+ * Covered: 1 <= top_k <= PS_SAMPLE_K_MAX, top_k < n_vocab, temperature > 0, at most PS_SAMPLE_WINDOW_MAX window entries;
+ * anything else is refused (rc 2), never served some other way. */
+#define PS_SAMPLE_K_MAX 256
+#define PS_SAMPLE_WINDOW_MAX 1024
+typedef struct ps_sample_cfg { /* the fields of the host's psh_sampler_cfg except the seed */
+    float temperature, top_p;
+    uint64_t top_k;
+    int32_t penalty_last_n;
+    float penalty_repeat, penalty_freq, penalty_present;
+    int32_t penalize_nl, ignore_eos, n_vocabs, special_eos_id, linefeed_id;
+} ps_sample_cfg;
+typedef struct ps_sample_state {
+    uint32_t mt[624];       /* std::mt19937's words and position (what libstdc++'s operator<< writes) */
+    uint32_t mt_pos;
+    int32_t n_window;       /* the counted repeat-penalty window: history[0 .. min(last_n, size)) (fixed for a whole run) */
+    int32_t window[PS_SAMPLE_WINDOW_MAX];
+    uint64_t n_outputs;     /* engine outputs consumed, accumulated */
+    uint64_t n_exact;       /* steps whose top-k took the exact libstdc++ heap path (ties / NaN), accumulated */
+} ps_sample_state;
+/* 0: the configuration is covered for this vocabulary size */
+int ps_hip_sample_covered(const ps_sample_cfg *cfg, int n_vocab, const ps_sample_state *state);
+/* one step on caller logits (device float[n_vocab]): *token_out (host) = the drawn token, *state advanced */
+int ps_hip_sample(ps_hip_ctx *ctx, const float *logits_dev, int n_vocab, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *token_out);
+/* ps_hip_model_decode_greedy with the drawn token in place of the arg-max: its own captured step (dropped where the greedy one is),
+ * eager in mode bit 0, hidden slots refused, one retry from the start state after an attention time-out.  *state advanced. */
+int ps_hip_model_decode_sampled(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids);
+/* diagnostics: [0] exact-path steps, [1] engine outputs, process-wide since the last reset (reset != 0 clears after reading) */
+void ps_hip_sample_counters(uint64_t *out2, int reset);
+const char *ps_hip_last_sample_kernels(void);
+
 const float *ps_hip_model_logits(const ps_hip_model *m); /* device [max_batch][vocab] */
 /* Arg-max ids of the most recent forward with lm_head (first maximum per token, what greedy_sample / TopK(1) returns: src/sampler/prob_array.cpp:65-67,
  * sampler.cpp:39-56), computed on the device behind the lm_head: 4 bytes per token come to the host instead of vocab x 4 (513 KB for 128 256 logits,

@@ -2,6 +2,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <sstream>
 
 namespace powerserve {
 
@@ -309,12 +310,45 @@ auto Model::generate(const std::vector<Token> &prompt, int steps, size_t batch_s
     return out;
 }
 
+// the device sampler's view of a standard chain: its configuration, its engine and its (fixed) penalty window.  false: not expressible
+bool device_sampler_state(const SamplerChain &sampler, ps_sample_cfg &c, ps_sample_state &st) {
+    const SamplerConfig &sc = sampler.config();
+    c = ps_sample_cfg{};
+    c.temperature = sc.temperature; c.top_p = sc.top_p; c.top_k = (uint64_t)sc.top_k;
+    c.penalty_last_n = sc.penalty_last_n; c.penalty_repeat = sc.penalty_repeat; c.penalty_freq = sc.penalty_freq; c.penalty_present = sc.penalty_present;
+    c.penalize_nl = sc.penalize_nl; c.ignore_eos = sc.ignore_eos; c.special_eos_id = sampler.eos_id(); c.linefeed_id = sampler.linefeed_id();
+    std::istringstream is(sampler.engine_state());
+    for (int i = 0; i < 624; i++) is >> st.mt[i];
+    is >> st.mt_pos;
+    const auto w = sampler.penalty_window();
+    if (is.fail() || w.size() > PS_SAMPLE_WINDOW_MAX) return false;
+    st.n_window = (int32_t)w.size();
+    std::copy(w.begin(), w.end(), st.window);
+    st.n_outputs = st.n_exact = 0;
+    return true;
+}
+
 auto Model::generate(const std::vector<Token> &prompt, int steps, size_t batch_size, SamplerChain &sampler) -> std::vector<Token> {
     std::vector<Token> out;
     if (steps <= 0 || prompt.empty()) return out;
     auto &id = m_config->model_id;
     m_platform->reset_kv_position(id);
     prefill(std::vector<Token>(prompt.begin(), prompt.end() - 1), batch_size); // the last prompt token is the first decode input (model.hpp:147-163)
+    ps_sample_cfg dc{};
+    static thread_local ps_sample_state ds; // (10 KB: not on the stack)
+    if (m_use_fused && m_device_sampling && sampler.standard() && device_sampler_state(sampler, dc, ds) &&
+        ps_hip_sample_covered(&dc, (int)m_config->llm.vocab_size, &ds) == 0) { // the chain inside the captured step, the engine comes back
+        backend().setup_threadpool();
+        out.resize(steps);
+        if (ps_hip_model_decode_sampled(backend().m_model, prompt.back(), steps, &dc, &ds, out.data()))
+            POWERSERVE_ABORT(std::string("decode_sampled: ") + ps_hip_last_error(backend().m_ctx));
+        backend().reset_threadpool();
+        for (Token t : out) sampler.accept(t);
+        std::string e;
+        for (int i = 0; i < 624; i++) e += std::to_string(ds.mt[i]) + ' ';
+        sampler.set_engine_state(e + std::to_string(ds.mt_pos));
+        return out;
+    }
     Token cur = prompt.back();
     for (int s = 0; s < steps; s++) {
         auto ret = forward({cur}, {(int)m_platform->get_kv_position(id)}, CausalAttentionMask(1), true);
@@ -349,6 +383,7 @@ void *psh_model_load(const char *model_dir, int device, int max_batch, int n_ctx
     } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }
 void psh_model_free(void *h) { delete (psh_model *)h; }
+void psh_model_set_device_sampling(void *h, int on) { ((psh_model *)h)->model->m_device_sampling = on != 0; } // 0: sampled generation keeps the host loop (A/B, tests)
 void psh_model_set_fused(void *h, int fused) { ((psh_model *)h)->model->m_use_fused = fused != 0; } // 0: plan() lowers nothing (A/B, tests)
 void psh_model_plan_stats(void *h, int *n_plans, int *n_lowered) { auto &be = ((psh_model *)h)->model->backend(); *n_plans = be.n_plans; *n_lowered = be.n_lowered; }
 int psh_model_plan_cache_hits(void *h) { return ((psh_model *)h)->model->n_plan_cache_hits; }

@@ -60,6 +60,7 @@ struct Model {
     std::set<std::pair<size_t, bool>> m_lowered_shapes;
     int n_plan_cache_hits = 0;
     bool m_use_fused    = true;  // HIPBackend::plan lowers the canonical graph to the fused launches; false: op-by-op (A/B, tests)
+    bool m_device_sampling = true; // generate(.., SamplerChain &): a standard chain the device covers runs inside the captured step; false: the host loop
 
     Model(const std::string &model_dir, const std::shared_ptr<ModelConfig> &config, const std::shared_ptr<Platform> &platform, int device,
           size_t max_batch);
@@ -96,6 +97,9 @@ using Qwen2Model = Model;
 
 auto load_model(const std::string &model_dir, const std::shared_ptr<Platform> &platform, int device = 0, size_t max_batch = 128, int n_ctx_cap = 0)
     -> std::shared_ptr<Model>;
+
+// the device sampler's view of a standard chain (configuration, engine, fixed penalty window); false: not expressible
+bool device_sampler_state(const SamplerChain &sampler, ps_sample_cfg &c, ps_sample_state &st);
 
 } // namespace powerserve
 

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <sstream>
 
 namespace powerserve {
 
@@ -151,6 +152,25 @@ void SamplerChain::build_from_config(const SamplerConfig &config, int32_t, Token
     append([p](ProbArray &c) { stage::top_p(c, p); });
     append(stage::normalize);
     append([this](ProbArray &c) { stage::draw(c, m_engine); });
+    m_config = config; m_eos = special_eos_id; m_linefeed = linefeed_id;
+    m_standard = true;
+}
+
+std::string SamplerChain::engine_state() const {
+    std::ostringstream os;
+    os << m_engine;
+    return os.str();
+}
+
+void SamplerChain::set_engine_state(const std::string &s) {
+    std::istringstream is(s);
+    is >> m_engine;
+    POWERSERVE_ASSERT(!is.fail());
+}
+
+std::vector<Token> SamplerChain::penalty_window() const {
+    const auto &h = m_penalty.history;
+    return std::vector<Token>(h.begin(), h.begin() + (std::ptrdiff_t)std::min((size_t)std::max(m_penalty.last_n, 0), h.size()));
 }
 
 void SamplerChain::apply(ProbArray &probs) {

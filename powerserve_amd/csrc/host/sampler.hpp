@@ -15,6 +15,7 @@
 #include <memory>
 #include <random>
 #include <span>
+#include <string>
 #include <vector>
 
 namespace powerserve {
@@ -86,14 +87,25 @@ struct SamplerChain final : Sampler {
     // n_vocabs / special_eos_id / linefeed_id are the vocabulary facts the reference reads from its Tokenizer
     SamplerChain(const SamplerConfig &config, int32_t n_vocabs, Token special_eos_id, Token linefeed_id) { build_from_config(config, n_vocabs, special_eos_id, linefeed_id); }
     void build_from_config(const SamplerConfig &config, int32_t n_vocabs, Token special_eos_id, Token linefeed_id);
-    void append(Stage s) { m_stages.push_back(std::move(s)); }
+    void append(Stage s) { m_stages.push_back(std::move(s)); m_standard = false; }
     void append(std::shared_ptr<Sampler> s); // a user stage: apply in place, accept forwarded
     void apply(ProbArray &probs) override;
     void accept(Token token) override;
     Token sample(std::span<const float> logits); // apply, take candidate 0, accept it
     uint64_t m_seed = 0;
+    // what the device sampler (include/ps_hip.h ps_hip_model_decode_sampled) needs to draw what this chain draws
+    bool standard() const { return m_standard && m_plugins.empty(); } // the configured stages and nothing else
+    const SamplerConfig &config() const { return m_config; }
+    Token eos_id() const { return m_eos; }
+    Token linefeed_id() const { return m_linefeed; }
+    std::string engine_state() const; // libstdc++'s operator<<: the 624 words, then the position
+    void set_engine_state(const std::string &s);
+    std::vector<Token> penalty_window() const; // the counted part of the repeat-penalty history
 
 private:
+    SamplerConfig m_config;
+    Token m_eos = stage::RepeatPenalty::none, m_linefeed = stage::RepeatPenalty::none;
+    bool m_standard = false;
     std::vector<Stage> m_stages;
     std::vector<std::shared_ptr<Sampler>> m_plugins;
     stage::RepeatPenalty m_penalty;

@@ -85,6 +85,10 @@ struct ps_hip_model {
     ps_step_state *state_sub = nullptr; // [64] per-chunk states of a super-chunk prefill (ps_hip_model_prefill)
     int attn_chunk = 0;                 // > 0 while such a forward is enqueued: the attention runs chunk by chunk
     hipGraphExec_t step_graph = nullptr;
+    hipGraphExec_t sample_graph = nullptr; // ps_hip_model_decode_sampled's captured step (dropped wherever step_graph is)
+    size_t sample_hint = 0;
+    ps_sample_dev *sample_dev = nullptr;   // sampler configuration + engine state of the current sampled run (allocated at first use)
+    void *sample_scratch = nullptr;
     hipGraphExec_t fwd1_graph[2] = {nullptr, nullptr}; // single-token forward without / with lm_head (the lowered op-API path)
     size_t fwd1_hint[2] = {0, 0};
     uint64_t weight_bytes = 0;
@@ -270,7 +274,7 @@ static int ensure_perf16(ps_hip_model *m) {
 
 // enqueue one forward over `bs` tokens whose ids are in tokens_dev and whose state is in m->state
 int g_kv_stream_force = getenv("PS_KV_STREAM") ? atoi(getenv("PS_KV_STREAM")) : -1; // ps_hip_debug_set(9, v)
-static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree, bool advance = false, bool use_rope_pos = false) {
+static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree, bool advance = false, bool use_rope_pos = false, bool sampled = false) {
     ps_hip_ctx *c = m->ctx;
     hipStream_t st = c->stream;
     const ps_llm_config &f = m->cfg;
@@ -436,7 +440,8 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
         gl.n_w = 1; gl.w[0] = ow; gl.out[0] = m->logits; gl.ldo[0] = f.vocab_size;
         gl.pro = 1; gl.pro_x = m->x; gl.pro_norm_w = m->output_norm; gl.pro_eps = f.norm_eps;
         if (mm(m, gl, a1, dim, bs)) return 2;
-        psl_argmax2(st, m->logits, f.vocab_size, bs, m->argmax_dev, m->am_v, m->am_i, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
+        if (sampled) psl_sample(st, m->logits, (int)f.vocab_size, m->sample_dev, m->sample_scratch, nullptr, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
+        else psl_argmax2(st, m->logits, f.vocab_size, bs, m->argmax_dev, m->am_v, m->am_i, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
     }
     PS_CHECK(c, hipGetLastError());
     return 0;
@@ -625,6 +630,7 @@ static int model_forward_impl(ps_hip_model *m, const int32_t *tokens, int n, con
 // from here on (mode bit 4): the forward that timed out has no valid result.  Expects the stream to be idle.
 static void drop_graphs(ps_hip_model *m) { // every captured launch plan (they bake the mode, the prefetch hint and the visibility pointers in)
     if (m->step_graph) { (void)hipGraphExecDestroy(m->step_graph); m->step_graph = nullptr; }
+    if (m->sample_graph) { (void)hipGraphExecDestroy(m->sample_graph); m->sample_graph = nullptr; }
     for (auto &g : m->fwd1_graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
 }
 // Every single-token forward that may have used the one-launch attention is followed, on the stream, by a 4-byte copy of the flag into pinned
@@ -889,6 +895,67 @@ static int decode_greedy_impl(ps_hip_model *m, int32_t token, int steps, int32_t
         c->err.clear();
         return decode_greedy_impl(m, token, steps, out_ids, true);
     }
+    m->position += (size_t)steps;
+    return 0;
+}
+
+// The greedy loop with the sampler chain in place of the arg-max (k_sample.hip): the configuration and the engine go to the device
+// once per run, the engine comes back at the end.  A time-out retry starts again from the caller's state, which is untouched until success.
+static int decode_sampled_impl(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids, bool retried);
+int ps_hip_model_decode_sampled(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids) {
+    return decode_sampled_impl(m, token, steps, cfg, state, out_ids, false);
+}
+static int decode_sampled_impl(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids, bool retried) {
+    ps_hip_ctx *c = m->ctx;
+    if (steps <= 0) return 0;
+    if (int rc = settle_pending(m)) return rc;
+    if (m->n_hidden) PS_FAIL(c, "decode_sampled: hidden KV slots (kv_mask) are not part of the captured step; unmask first");
+    if (m->position + (size_t)steps > m->cfg.seq_len) PS_FAIL(c, "decode_sampled: KV cache would overflow n_ctx");
+    if (token < 0 || (uint32_t)token >= m->cfg.vocab_size) PS_FAIL(c, "decode_sampled: token id out of range");
+    static ps_sample_dev h; // (staging of the upload / read-back; the stream is idle between the two)
+    {
+        std::string err;
+        if (psl_sample_pack(cfg, state, (int)m->cfg.vocab_size, &h, &err)) { c->err = "decode_sampled: " + err; return 2; }
+    }
+    PS_CHECK(c, hipSetDevice(c->device));
+    if (!m->sample_dev && (dmalloc(m, (void **)&m->sample_dev, sizeof(ps_sample_dev)) || dmalloc(m, &m->sample_scratch, psl_sample_scratch_bytes((int)m->cfg.vocab_size)))) return 1;
+    m->pin_argmax_n = 0;
+    PS_CHECK(c, hipMemcpyAsync(m->sample_dev, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+    PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, &token, 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, (int)m->position, 1, 0);
+    PS_CHECK(c, hipStreamSynchronize(c->stream));
+    int s = 0;
+    if (m->sample_graph && (m->position < m->sample_hint || m->position >= m->sample_hint + 1024)) { (void)hipGraphExecDestroy(m->sample_graph); m->sample_graph = nullptr; }
+    if ((m->mode & 1) == 0 && !m->sample_graph) {
+        if (int rc = enqueue_forward(m, 1, true, false, true, false, true)) return rc;
+        PS_CHECK(c, hipStreamSynchronize(c->stream));
+        s = 1;
+        hipGraph_t g = nullptr;
+        m->sample_hint = m->position;
+        PS_CHECK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        int rc = enqueue_forward(m, 1, true, false, true, false, true);
+        hipError_t e = hipStreamEndCapture(c->stream, &g);
+        if (rc || e != hipSuccess) { c->err = "decode_sampled: graph capture failed: " + c->err; if (g) (void)hipGraphDestroy(g); return 2; }
+        PS_CHECK(c, hipGraphInstantiate(&m->sample_graph, g, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(g);
+    }
+    for (; s < steps; s++) {
+        if ((m->mode & 1) == 0) {
+            PS_CHECK(c, hipGraphLaunch(m->sample_graph, c->stream));
+        } else {
+            if (int rc = enqueue_forward(m, 1, true, false, true, false, true)) return rc;
+        }
+    }
+    note_single_token(m);
+    PS_CHECK(c, hipMemcpyAsync(out_ids, m->ids_dev, (size_t)steps * 4, hipMemcpyDeviceToHost, c->stream));
+    PS_CHECK(c, hipMemcpyAsync(&h, m->sample_dev, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    PS_CHECK(c, hipStreamSynchronize(c->stream));
+    if (const int rc = check_attn_timeout(m, "decode_sampled")) {
+        if (rc != PS_HIP_ATTN_TIMEOUT || retried) return rc;
+        c->err.clear();
+        return decode_sampled_impl(m, token, steps, cfg, state, out_ids, true);
+    }
+    psl_sample_unpack(&h, state);
     m->position += (size_t)steps;
     return 0;
 }

@@ -68,3 +68,23 @@ void psl_argmax2(hipStream_t st, const float *src, int64_t n, int64_t rows, int3
 
 // host restatement of ggml_rope_cache_init for positions [0, n_pos) -> table[n_pos][ne0]
 void ps_rope_table_host(const ps_rope_params *rp, int64_t ne0, const int32_t *pos, int n_pos, float *table);
+
+// device sampler (k_sample.hip): configuration + engine state in one device buffer, so that a captured step serves every
+// configuration; the host packs it from ps_sample_cfg / ps_sample_state (psl_sample_pack) and reads the engine back (psl_sample_unpack)
+struct ps_sample_dev {
+    uint32_t mt[624];
+    uint32_t mt_pos;
+    int32_t k;
+    float temperature, top_p, repeat, freq, present;
+    int32_t ban_id;   // EOS entry set to -inf (ignore_eos), -1: none
+    int32_t spare_id; // line feed left unpenalised (!penalize_nl), -1: none
+    int32_t n_pen;    // distinct tokens of the counted window (0: penalty inactive)
+    uint64_t n_outputs, n_exact;
+    int32_t pen_tok[PS_SAMPLE_WINDOW_MAX], pen_cnt[PS_SAMPLE_WINDOW_MAX];
+};
+int psl_sample_pack(const ps_sample_cfg *c, const ps_sample_state *s, int n_vocab, ps_sample_dev *out, std::string *err);
+void psl_sample_unpack(const ps_sample_dev *d, ps_sample_state *s);
+size_t psl_sample_scratch_bytes(int n_vocab);
+// penalty + top-k + tail + draw of one row of n logits; token_out (device) optional; with state != NULL also the decode
+// bookkeeping of psl_argmax2: token[0] = id, ids[state->n_out++] = id, state->pos0++
+void psl_sample(hipStream_t st, const float *logits, int n, ps_sample_dev *d, void *scratch, int32_t *token_out, ps_step_state *state, int32_t *tokens, int32_t *ids);

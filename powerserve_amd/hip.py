@@ -33,7 +33,47 @@ EXPORTS = [
     "ps_hip_model_forward", "ps_hip_model_decode_greedy", "ps_hip_model_logits", "ps_hip_model_scratch", "ps_hip_model_k_cache",
     "ps_hip_model_v_cache", "ps_hip_model_weight_bytes_per_token", "ps_hip_model_set_mode", "ps_hip_model_bench_gemv", "ps_hip_model_bench_matmul", "ps_hip_debug_timeline", "ps_hip_last_matmul_kernel", "ps_hip_last_attention_kernel", "ps_hip_debug_set", "ps_hip_debug_f16_gemm", "ps_hip_model_forward_tree", "ps_hip_model_prefill", "ps_hip_model_forward_lowered", "ps_hip_model_sync_check", "ps_hip_model_kv_mask",
     "ps_hip_soft_max", "ps_hip_model_kv_copy", "ps_hip_model_kv_save_tokens", "ps_hip_model_kv_unmask_tokens", "ps_hip_model_kv_append_tokens", "ps_hip_model_argmax",
+    "ps_hip_sample_covered", "ps_hip_sample", "ps_hip_model_decode_sampled", "ps_hip_sample_counters", "ps_hip_last_sample_kernels",
 ]
+SAMPLE_K_MAX, SAMPLE_WINDOW_MAX = 256, 1024  # PS_SAMPLE_K_MAX, PS_SAMPLE_WINDOW_MAX (include/ps_hip.h)
+
+
+class SampleCfg(C.Structure):
+    """ps_sample_cfg: the fields of host.SamplerCfg (psh_sampler_cfg) except the seed."""
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_uint64),
+                ("penalty_last_n", C.c_int32), ("penalty_repeat", C.c_float), ("penalty_freq", C.c_float),
+                ("penalty_present", C.c_float), ("penalize_nl", C.c_int32), ("ignore_eos", C.c_int32), ("n_vocabs", C.c_int32),
+                ("special_eos_id", C.c_int32), ("linefeed_id", C.c_int32)]
+
+    @classmethod
+    def from_host(cls, h):
+        """from a host.SamplerCfg"""
+        return cls(h.temperature, h.top_p, h.top_k, h.penalty_last_n, h.penalty_repeat, h.penalty_freq, h.penalty_present,
+                   h.penalize_nl, h.ignore_eos, h.n_vocabs, h.special_eos_id, h.linefeed_id)
+
+
+class SampleState(C.Structure):
+    """ps_sample_state: std::mt19937's words + position, the counted penalty window, and the accumulated diagnostics."""
+    _fields_ = [("mt", C.c_uint32 * 624), ("mt_pos", C.c_uint32), ("n_window", C.c_int32), ("window", C.c_int32 * SAMPLE_WINDOW_MAX),
+                ("n_outputs", C.c_uint64), ("n_exact", C.c_uint64)]
+
+    @classmethod
+    def seeded(cls, seed: int, window=()):
+        """std::mt19937(seed) (the chain seeds with the configured seed) and a penalty window"""
+        s = cls()
+        x = [seed & 0xffffffff]
+        for i in range(1, 624):
+            x.append((1812433253 * (x[-1] ^ (x[-1] >> 30)) + i) & 0xffffffff)
+        s.mt[:] = x
+        s.mt_pos = 624
+        w = list(window)
+        s.n_window = len(w)
+        s.window[:len(w)] = w
+        return s
+
+    def engine(self):
+        return np.array(self.mt[:], dtype=np.uint32), int(self.mt_pos)
+
 
 
 class PSTensor(C.Structure):
@@ -124,6 +164,9 @@ def lib() -> C.CDLL:
         "ps_hip_last_matmul_kernel": (C.c_char_p, []),
         "ps_hip_last_attention_kernel": (C.c_char_p, []),
         "ps_hip_debug_set": (i32, [i32, i32]),
+        "ps_hip_sample_covered": (i32, [vp, i32, vp]), "ps_hip_sample": (i32, [vp, vp, i32, vp, vp, vp]),
+        "ps_hip_model_decode_sampled": (i32, [vp, i32, i32, vp, vp, vp]), "ps_hip_sample_counters": (None, [vp, i32]),
+        "ps_hip_last_sample_kernels": (C.c_char_p, []),
         "ps_hip_debug_f16_gemm": (i32, [vp, i32, C.c_int64, C.c_int64, i32, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -420,6 +463,12 @@ class Model:
         self.ctx.check(self.ctx.L.ps_hip_model_decode_greedy(self.h, int(token), steps, _ptr(out)))
         return out
 
+    def decode_sampled(self, token: int, steps: int, cfg: SampleCfg, state: SampleState) -> np.ndarray:
+        """decode_greedy with the standard sampler chain in place of the arg-max; `state` (engine, window) is advanced in place."""
+        out = np.empty(steps, dtype=np.int32)
+        self.ctx.check(self.ctx.L.ps_hip_model_decode_sampled(self.h, int(token), steps, C.byref(cfg), C.byref(state), _ptr(out)))
+        return out
+
     def generate(self, prompt, batch_size: int, steps: int):
         """ModelTokenIterator semantics (src/model/model.hpp:117-184): prefill all but the last prompt token in
         chunks of batch_size without lm_head, then `steps` greedy single-token steps."""
@@ -448,3 +497,25 @@ class Model:
         out = np.empty((self.cfg.kv_dim, self.cfg.seq_len), dtype=np.float32)
         self.ctx.check(self.ctx.L.ps_hip_memcpy_d2h(self.ctx.h, _ptr(out), self.ctx.L.ps_hip_model_v_cache(self.h, layer), out.nbytes))
         return out
+
+
+def sample(ctx: Ctx, logits_dev: int, n_vocab: int, cfg: SampleCfg, state: SampleState) -> int:
+    """One step of the device sampler chain on device logits (a pointer to n_vocab floats); `state` is advanced in place."""
+    tok = C.c_int32(-1)
+    ctx.check(ctx.L.ps_hip_sample(ctx.h, C.c_void_p(logits_dev), int(n_vocab), C.byref(cfg), C.byref(state), C.byref(tok)))
+    return int(tok.value)
+
+
+def sample_covered(cfg: SampleCfg, n_vocab: int, state: SampleState | None = None) -> bool:
+    return lib().ps_hip_sample_covered(C.byref(cfg), int(n_vocab), C.byref(state if state is not None else SampleState())) == 0
+
+
+def sample_counters(reset: bool = False):
+    """(exact-path steps, engine outputs) since the last reset, process-wide"""
+    out = (C.c_uint64 * 2)()
+    lib().ps_hip_sample_counters(out, int(reset))
+    return int(out[0]), int(out[1])
+
+
+def last_sample_kernels() -> str:
+    return lib().ps_hip_last_sample_kernels().decode()

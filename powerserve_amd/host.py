@@ -12,7 +12,10 @@ LIB_PATH = os.path.join(HERE, "lib", "libps_host.so")
 EXPORTS = ["psh_last_error", "psh_model_load", "psh_model_free", "psh_model_set_fused", "psh_model_plan_stats", "psh_model_kv_position", "psh_model_reset",
            "psh_model_vocab", "psh_model_forward", "psh_model_generate", "psh_spec_generate", "psh_spec_generate_sampled", "psh_draft_sample", "psh_sampler_create", "psh_sampler_free", "psh_sampler_sample",
            "psh_model_generate_sampled", "psh_token_tree_run", "psh_gguf_summary", "psh_config_summary",
-           "psh_model_decode", "psh_model_prefill", "psh_model_plan_cache_hits", "psh_model_set_plan_cache", "psh_graph_softmax", "psh_backend_get_n_tasks", "psh_backend_add_cache", "psh_model_kv_read", "psh_kv_op"]
+           "psh_model_decode", "psh_model_prefill", "psh_model_plan_cache_hits", "psh_model_set_plan_cache", "psh_graph_softmax", "psh_backend_get_n_tasks", "psh_backend_add_cache", "psh_model_kv_read", "psh_kv_op",
+           "psh_model_set_device_sampling", "psh_sampler_engine_state", "psh_sampler_device_state", "psh_sampler_is_standard", "psh_sampler_append_noop", "psh_model_generate_with_chain",
+           "psh_debug_mt_seed", "psh_debug_mt_next", "psh_debug_discrete", "psh_debug_partial_sort", "psh_debug_chain", "psh_debug_std_mt",
+           "psh_debug_std_mt_seed", "psh_debug_std_discrete", "psh_debug_std_partial_sort"]
 _LIB = None
 
 
@@ -58,6 +61,22 @@ def lib() -> C.CDLL:
         L.psh_config_summary.restype = C.c_int64
         L.psh_config_summary.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.psh_gguf_summary.restype = C.c_int64
+        L.psh_model_set_device_sampling.argtypes = [C.c_void_p, C.c_int]
+        L.psh_sampler_engine_state.argtypes = [C.c_void_p, C.c_void_p]
+        L.psh_sampler_device_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.psh_sampler_is_standard.argtypes = [C.c_void_p]
+        L.psh_sampler_append_noop.argtypes = [C.c_void_p]
+        L.psh_model_generate_with_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.psh_debug_mt_seed.argtypes = [C.c_void_p, C.c_uint32]
+        L.psh_debug_mt_next.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.psh_debug_discrete.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.psh_debug_partial_sort.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.psh_debug_chain.restype = C.c_int32
+        L.psh_debug_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.psh_debug_std_mt.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.psh_debug_std_mt_seed.argtypes = [C.c_void_p, C.c_uint32]
+        L.psh_debug_std_discrete.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.psh_debug_std_partial_sort.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.psh_gguf_summary.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         _LIB = L
     return _LIB
@@ -179,6 +198,10 @@ class HostModel:
         if r < 0:
             raise HostError(self.L.psh_last_error().decode())
         return int(r)
+
+    def set_device_sampling(self, on: bool):
+        """False: Model::generate with a sampler chain keeps the host loop (logits to the host every step) -- A/B runs, tests"""
+        self.L.psh_model_set_device_sampling(self.h, int(on))
 
     def generate(self, prompt, batch_size: int, steps: int):
         p = np.ascontiguousarray(prompt, dtype=np.int32)
@@ -329,6 +352,11 @@ def token_tree_run(target, draft, cfg: SpecConfig, root_token: int, n_iterations
     return out[:n_out[0]].copy(), [tree[i, :n_nodes[i]].copy() for i in range(n_iterations)], {k: int(v) for k, v in zip(keys, st)}
 
 
+class MtState(C.Structure):
+    """std::mt19937's state as libstdc++ keeps it (csrc/ps_sample_dev.h ps_mt_state)"""
+    _fields_ = [("x", C.c_uint32 * 624), ("p", C.c_uint32)]
+
+
 class Sampler:
     """SamplerChain of the C++ mirror (csrc/host/sampler.cpp): sample(logits) = apply + probs[0] + accept."""
 
@@ -338,6 +366,28 @@ class Sampler:
         self.h = self.L.psh_sampler_create(C.byref(cfg))
         if not self.h:
             raise HostError(self.L.psh_last_error().decode())
+
+    def engine_state(self):
+        """the chain's std::mt19937: (624 words, position), what libstdc++'s operator<< writes"""
+        st = MtState()
+        self.L.psh_sampler_engine_state(self.h, C.byref(st))
+        return np.array(st.x[:], dtype=np.uint32), int(st.p)
+
+    def device_state(self):
+        """(hip.SampleCfg, hip.SampleState) that make the device sampler draw what this chain draws next"""
+        from . import hip
+        c, st = hip.SampleCfg(), hip.SampleState()
+        if self.L.psh_sampler_device_state(self.h, C.byref(c), C.byref(st)):
+            raise HostError("the chain's state is not expressible for the device sampler")
+        c.n_vocabs = self.cfg.n_vocabs
+        return c, st
+
+    def is_standard(self) -> bool:
+        return bool(self.L.psh_sampler_is_standard(self.h))
+
+    def append_noop(self):
+        """splice in a plug-in stage that changes nothing: the chain is no longer the standard one"""
+        self.L.psh_sampler_append_noop(self.h)
 
     def sample(self, logits) -> int:
         lg = np.ascontiguousarray(logits, dtype=np.float32)
@@ -358,6 +408,16 @@ def generate_sampled(model: HostModel, prompt, batch_size: int, steps: int, cfg:
     p = np.ascontiguousarray(prompt, dtype=np.int32)
     out = np.empty(steps, dtype=np.int32)
     if L.psh_model_generate_sampled(model.h, p.ctypes.data, p.size, batch_size, steps, C.byref(cfg), out.ctypes.data):
+        raise HostError(L.psh_last_error().decode())
+    return out
+
+
+def generate_with(model: HostModel, prompt, batch_size: int, steps: int, sampler: "Sampler"):
+    """Model::generate with the caller's chain (its engine and penalty history carry on from where they are, and advance)"""
+    L = lib()
+    p = np.ascontiguousarray(prompt, dtype=np.int32)
+    out = np.empty(steps, dtype=np.int32)
+    if L.psh_model_generate_with_chain(model.h, p.ctypes.data, p.size, batch_size, steps, sampler.h, out.ctypes.data):
         raise HostError(L.psh_last_error().decode())
     return out
 
