@@ -20,6 +20,8 @@
 // write-through (sc1), drained, then ticketed; the reader polls ONE word, and the lines it then reads with plain loads are lines this launch has not touched before
 // (the new K row, the 128-byte lines of the V rows that hold the new column, q, the score rows) -- so neither an L1 nor an L2 anywhere holds an older copy.  That is why
 // the cached K rows are requested only BELOW the position and the V rows only up to the last whole line below it.  Placement (block b on XCD b % 8) is for speed only.
+// That is the counter form of rendezvous A (ps_hip_debug_set(11, 1)); by default q, the new K row and the new V values are handed over as tagged granules instead
+// (round 7, qa_store_granule below): read by sc1 loads only, so no plain load reads anything handed over in the launch.
 #include "ps_expf.h"
 #include "ps_g4_dev.h"
 #include "ps_ops.h"
@@ -40,6 +42,7 @@ struct QAParams {
     float eps;
     int nq, nk;                    // row groups of ONE kv head in Wq and in Wk (= Wv)
     int split_q, split_r;          // tasks of a workgroup: split_q (+ 1 for the first split_r workgroups of its kv head)
+    unsigned long long *gran;      // rendezvous A as tagged granules (psl_attn_args::gran), or null: the counter hand-off
     psl_attn_args a;
 };
 
@@ -57,6 +60,18 @@ __device__ __forceinline__ void qa_rendezvous(unsigned *ctr, const unsigned base
         __builtin_amdgcn_s_sleep(1);
         if (++spins > (1 << 16)) { __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; } // never hang the GPU: the host turns the flag into a re-run on the unfused launches
     }
+}
+
+// Rendezvous A as tagged granules (round 7).  What a workgroup needs from the others before its scores is small -- r2 q rows, the new K row and its four
+// channels of the new V column: (r2 + 1) * head_size + 4 floats, 2.6 KB for 8B -- so the data IS the flag (MI355X_MICROARCH.md, handoff-1to1 vs handoff-flag):
+// the chain wave writes each value as ONE naturally aligned 8-byte {tag, value bits} granule with ONE sc1 store and neither drains nor tickets; one wave of every
+// reader sweeps its granules with sc1 loads (global, 8 bytes, no nt) until every tag is this launch's.  Layout per kv head: [r2 * hs q | hs K | hs V].
+// The tag is this launch's epoch + 1 (never 0: the buffer is zeroed with the counters) from rendezvous B's never-reset counter, read at entry -- every workgroup
+// adds to it exactly once per launch, whatever happens, and none of this launch can have added before this one has stored its granules, whose values depend
+// on what it read.  A granule is written once per launch and the launches of a stream do not overlap, so a granule with this tag is this launch's value.
+typedef __attribute__((address_space(1))) unsigned long long qa_gu64;
+__device__ __forceinline__ void qa_store_granule(unsigned long long *g, unsigned tag, float v) {
+    __hip_atomic_store((qa_gu64 *)g, ((unsigned long long)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 template <int NV, int KVS> // head_size / 32; the cache is streamed (non-temporal loads: see above)
@@ -112,6 +127,13 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
     int pos0 = 0;
     float4 kf[PASSES][NV]; // waves 0-7: K row of this lane's position in each pass
     unsigned baseA = 0, baseB = 0; // the rendezvous counters as they stood at entry (wave 8, lane 0: qa_rendezvous)
+    // waves 0-7: zeros past the cache length in the V rows (with granules before rendezvous A: it takes nothing from it)
+    auto v_zero_tail = [&]() {
+        for (int col = ((pos0 + 4) & ~3) + 4 * tid; col < RS - 36; col += 4 * NT) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) *(float4 *)(vt + k * RS + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
 
     if (wave < NW) { // ================================================================== mat-vec phase: producers (k_gemv4.hip, PRO 1, XW 2, YS 0)
         constexpr int PPW = 1; // K <= 4096: 8 pairs of tiles, one per producer
@@ -279,6 +301,8 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
             epA[tl * 8 + r] = va; epB[tl * 8 + r] = vb; epC[tl * 8 + r] = vc;
         }
         __syncthreads(); // #2
+        const unsigned tagA = (unsigned)__builtin_amdgcn_readfirstlane((int)baseB) / (unsigned)G + 1u; // (granules: every lane is active here, lane 0 read the counter)
+        unsigned long long *const gran = p.gran ? p.gran + (size_t)kvh * (r2 + 2) * hs : nullptr;
         __builtin_amdgcn_s_setprio(3);
         float acc0 = 0.f, acc1 = 0.f, accm = 0.f;
         int tl = 0, un = 0;
@@ -294,6 +318,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
             const float vp = dpp_f<0x128>(v); // partner row of the rotation pair
             if (u == 0) { // everything another workgroup reads after rendezvous A is stored write-through
                 if (wi == 2) {
+                    if (gran) qa_store_granule(gran + (r2 + 1) * hs + (int)(row - (int64_t)kvh * hs), tagA, v);
                     qa_store_f(a.v_cache + row * a.n_ctx + kv_pos, v);
                 } else {
                     const int e = (int)(row % hs);
@@ -302,6 +327,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
                         const float x0 = (e & 1) ? vp : v, x1 = (e & 1) ? v : vp;
                         res = ps_rope_one(x0, x1, ea, eb, (e & 1) != 0);
                     }
+                    if (gran) qa_store_granule(gran + (wi == 0 ? (int)(row - (int64_t)kvh * r2 * hs) : r2 * hs + (int)(row - (int64_t)kvh * hs)), tagA, res);
                     if (wi == 0) qa_store_f(a.q + row, res); else qa_store_f(a.k_cache + (int64_t)kv_pos * kvd + row, res);
                 }
             }
@@ -339,14 +365,61 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
         }
         __builtin_amdgcn_s_setprio(0);
         mark(1); // rows stored
-        // ---- rendezvous A: this workgroup's q / k / v are drained, then its ticket
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads(); // A0
-        if (lane == 0) qa_rendezvous(a.tick + kvh * 64 + 32, baseA, (unsigned)G, a.sync + 31);
-        asm volatile("" ::: "memory");
-        mark(2); // rendezvous A complete
+        if (gran) { // ---- rendezvous A, granules: no drain, no ticket; this wave sweeps the kv head's q and K row and this workgroup's four V values
+            __syncthreads(); // A0
+            // first, what the attention prologue reads that nobody writes in this launch -- the soft-max table and the lines of the V rows that hold the new
+            // column (that column is this launch's: taken from the granules below) -- asked for by THIS wave, whose memory queue holds no V pieces
+            const int vlim = pos0 & ~31, nkv4 = (pos0 + 4) & ~3, lrow = lane >> 3, lcol = vlim + 4 * (lane & 7); // (n_kv rounded up to 4 <= n_ctx: in bounds)
+            const bool lline = lane < 32 && lcol < nkv4;
+            uint64_t et = 0;
+            float4 vl = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (lane < PS_EXP2F_N) et = ps_exp2f_tab[lane];
+            if (lline) vl = *(const float4 *)(vbase + (int64_t)lrow * a.n_ctx + lcol);
+            const int nqk = (r2 + 1) * hs; // granule i < nqk: q, then K; nqk .. nqk + 3: V channels bx * 4 .. bx * 4 + 3 (nqk is a multiple of 64: one slot)
+            constexpr int SLOTS = (5 * hs + 4 + 63) / 64;
+            const qa_gu64 *src[SLOTS];
+            unsigned val[SLOTS];
+#pragma unroll
+            for (int k = 0; k < SLOTS; k++) {
+                const int i = k * 64 + lane;
+                src[k] = (const qa_gu64 *)(gran + (i < nqk ? i : (i < nqk + 4 ? nqk + bx * 4 + (i - nqk) : 0)));
+            }
+            for (int spins = 0;;) { // every pass re-reads every granule: each is written once per launch
+                unsigned long long x[SLOTS];
+#pragma unroll
+                for (int k = 0; k < SLOTS; k++) x[k] = __hip_atomic_load(src[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                bool ok = true;
+#pragma unroll
+                for (int k = 0; k < SLOTS; k++) {
+                    val[k] = (unsigned)x[k];
+                    ok &= k * 64 + lane >= nqk + 4 || (unsigned)(x[k] >> 32) == tagA;
+                }
+                if (__all(ok)) break;
+                __builtin_amdgcn_s_sleep(1);
+                if (++spins > (1 << 16)) { if (lane == 0) __hip_atomic_store(a.sync + 31, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; } // (qa_rendezvous's budget and flag)
+            }
+            // into the LDS slots the attention reads: q -> qs, the K row -> sst (free until the scores), the V lines, then (later in this wave's LDS order) the new column over them
+            if (lane < PS_EXP2F_N) etab[lane] = et;
+            if (lline) *(float4 *)(vt + lrow * RS + lcol) = vl;
+#pragma unroll
+            for (int k = 0; k < SLOTS; k++) {
+                const int i = k * 64 + lane;
+                if (i < r2 * hs) qs[i] = __uint_as_float(val[k]);
+                else if (i < nqk) sst[i - r2 * hs] = __uint_as_float(val[k]);
+                else if (i < nqk + 4) vt[(i - nqk) * RS + pos0] = __uint_as_float(val[k]);
+            }
+            mark(2); // granules swept
+        } else {
+            // ---- rendezvous A: this workgroup's q / k / v are drained, then its ticket
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads(); // A0
+            if (lane == 0) qa_rendezvous(a.tick + kvh * 64 + 32, baseA, (unsigned)G, a.sync + 31);
+            asm volatile("" ::: "memory");
+            mark(2); // rendezvous A complete
+        }
     }
-    __syncthreads(); // ==== A: q, the new K row and the new V column of this kv head are in memory
+    if (p.gran && wave < NW) v_zero_tail();
+    __syncthreads(); // ==== A: q, the new K row and the new V column of this kv head are in memory (counter) / in LDS (granules)
     mark(6);
 
     // ================================================================================== attention phase (attn_decode2_kernel<NV, 512>; wave 8 only keeps the barriers company)
@@ -356,26 +429,32 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
     const int ntail = n_kv - n8, nleft = n_kv - np;
     const int nq4 = r2 * hs / 4;
     if (aw) {
-        // q of this kv head's heads (once per workgroup, through LDS), the lines of the V rows that hold the new column; zeros past the cache length
-        if (tid < nq4) *(float4 *)(qs + tid * 4) = *(const float4 *)(a.q + (int64_t)kvh * r2 * hs + tid * 4);
-        if (tid < PS_EXP2F_N) etab[tid] = ps_exp2f_tab[tid];
-        const int vlim = pos0 & ~31, nkv4 = (n_kv + 3) & ~3; // (n_kv rounded up to 4 <= n_ctx: in bounds)
-        if (tid < 32) {
-            const int row = tid >> 3, col = vlim + 4 * (tid & 7);
-            if (col < nkv4) *(float4 *)(vt + row * RS + col) = *(const float4 *)(vbase + (int64_t)row * a.n_ctx + col);
-        }
-        for (int col = nkv4 + 4 * tid; col < RS - 36; col += 4 * NT) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) *(float4 *)(vt + k * RS + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!p.gran) {
+            // q of this kv head's heads (once per workgroup, through LDS), the lines of the V rows that hold the new column; zeros past the cache length
+            if (tid < nq4) *(float4 *)(qs + tid * 4) = *(const float4 *)(a.q + (int64_t)kvh * r2 * hs + tid * 4);
+            if (tid < PS_EXP2F_N) etab[tid] = ps_exp2f_tab[tid];
+            const int vlim = pos0 & ~31, nkv4 = (n_kv + 3) & ~3; // (n_kv rounded up to 4 <= n_ctx: in bounds)
+            if (tid < 32) {
+                const int row = tid >> 3, col = vlim + 4 * (tid & 7);
+                if (col < nkv4) *(float4 *)(vt + row * RS + col) = *(const float4 *)(vbase + (int64_t)row * a.n_ctx + col);
+            }
+            v_zero_tail();
         }
 #pragma unroll
         for (int ps = 0; ps < PASSES; ps++) { // the new K row: the wave that owns the new position asks for its eight rows once more (the old ones are cache hits)
             const int sl = bx + ((uw >> 2) + SPP * ps) * G, j0 = sl * 32 + (uw & 3) * 8, j = j0 + p8;
             if (j0 <= pos0 && pos0 < j0 + 8) { // (uniform)
-                const float *kr = kb + (int64_t)(j <= pos0 ? j : 0) * kvd;
-                if (!KVS || j == pos0 || j0 == pos0) { // (KVS: the old rows were streamed past the caches -- only the new row, or the whole group when nobody has asked for it yet)
+                if (p.gran) { // granules: the new row from LDS (lanes past it score it too: nobody reads those scores), the older rows are request_k's
+                    if (j >= pos0) {
 #pragma unroll
-                    for (int m = 0; m < NV; m++) kf[ps][m] = *(const float4 *)(kr + m * 32);
+                        for (int m = 0; m < NV; m++) kf[ps][m] = *(const float4 *)(sst + m * 32 + 4 * tq);
+                    }
+                } else {
+                    const float *kr = kb + (int64_t)(j <= pos0 ? j : 0) * kvd;
+                    if (!KVS || j == pos0 || j0 == pos0) { // (KVS: the old rows were streamed past the caches -- only the new row, or the whole group when nobody has asked for it yet)
+#pragma unroll
+                        for (int m = 0; m < NV; m++) kf[ps][m] = *(const float4 *)(kr + m * 32);
+                    }
                 }
             }
         }
@@ -610,6 +689,7 @@ size_t qa_lds_bytes(const QAParams &p, int hs) {
 } // namespace
 
 int g_qa_force = 0; // ps_hip_debug_set(7, v)
+int g_qa_counter = getenv("PS_QA_COUNTER") ? atoi(getenv("PS_QA_COUNTER")) : 0; // ps_hip_debug_set(11, v): 1 = rendezvous A on the counter (round 6's hand-off) instead of granules
 
 // Q / K / V mat-vec (RMSNorm + quantizer prologue, RoPE + KV append) + single-token attention in ONE launch.  false: not covered -- the caller issues the two launches.
 bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, const psl_attn_args &a) {
@@ -652,6 +732,8 @@ bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, c
     const int max_units = (p.split_q + (p.split_r ? 1 : 0)) * p.n_units;
     p.rec_units = (max_units + 31) / 32 * 32;
     p.a = a;
+    extern int g_qa_counter;
+    p.gran = g_qa_counter ? nullptr : a.gran;
     const size_t lds = qa_lds_bytes(p, hs);
     if (lds > 160 * 1024) return false;
     static unsigned long long attr = 0;

@@ -59,6 +59,7 @@ struct ps_hip_model {
     bool attn1_disabled = false;        // the one-launch attention timed out once on this device: mode bit 4 is sticky (set_mode ORs it back in; bit 6 re-arms)
     float *attn_xchg = nullptr;    // attn_decode2: scores in flight between workgroups (k_attn.hip)
     unsigned *attn_tick = nullptr; // attn_decode2: [64 * kv head] arrival counters
+    unsigned long long *attn_gran = nullptr; // the fused Q / K / V + attention launch: rendezvous A's granules (k_qkvattn.hip)
     size_t graph_hint = 0;                   // KV position the captured step was given as its prefetch hint (n_kv_lo)
     int n_kv_hint = 0;             // capture of a single-token forward: the lower bound of n_kv its prefetch hint is baked with
     int n_kv_host = 0;             // pos0 + bs of the forward being enqueued eagerly (0 while a graph is captured / replayed)
@@ -302,7 +303,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
     const bool f16 = (m->mode & 32) && bs >= 2 && !lm_head && !use_tree && !use_rope_pos;
     if (f16) if (int rc = ensure_perf16(m)) return rc;
     const bool one_launch = (m->mode & 16) == 0; // default; mode bit 4 switches attn_decode2 off (two launches)
-    aa.xchg = m->attn_xchg; aa.tick = m->attn_tick;
+    aa.xchg = m->attn_xchg; aa.tick = m->attn_tick; aa.gran = m->attn_gran;
     // Single-token attention: are the cached K rows / V channels read with non-temporal loads (psl_attn_args::kv_stream)?  Measured (profiles/r06_kv_stream_threshold.txt,
     // r06_ad2_nt_small_models.txt): the fused Q / K / V + attention launch is faster with them at every cache length tried (8B: +1.0 % behind a 256-token prompt, +1.6 % behind
     // 1024, +2.2 % behind 2048); the attention launch of its own (attn_decode2) gains where the whole cache -- every layer, K and V -- is more than the memory-side cache keeps
@@ -504,6 +505,7 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
         dmalloc(m, (void **)&m->g1, mb * hid * 4) || dmalloc(m, (void **)&m->u1, mb * hid * 4) ||
         dmalloc(m, (void **)&m->attn_sync, 2048 * 4) ||
         dmalloc(m, (void **)&m->attn_xchg, psl_attn_decode2_xchg_bytes((int)f.n_kv_heads, (int)nctx)) || dmalloc(m, (void **)&m->attn_tick, (size_t)f.n_kv_heads * 64 * 4) ||
+        dmalloc(m, (void **)&m->attn_gran, (size_t)(f.n_heads + 2 * f.n_kv_heads) * f.head_size * 8) ||
         dmalloc(m, (void **)&m->scores, mb * f.n_heads * nctx * 4) || dmalloc(m, (void **)&m->logits, mb * f.vocab_size * 4) ||
         dmalloc(m, (void **)&m->rope_table, nctx * f.head_size * 4) ||
         dmalloc(m, &m->act_mem, ps_act_bytes(dim > hid ? dim : hid, mb)) ||
@@ -523,6 +525,7 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
     if (hipHostMalloc((void **)&m->pin_tokens, (2 * mb + 16) * 4, hipHostMallocDefault) != hipSuccess) return fail();
     m->pin_argmax = m->pin_tokens + mb;
     (void)hipMemsetAsync(m->attn_tick, 0, (size_t)f.n_kv_heads * 64 * 4, c->stream);
+    (void)hipMemsetAsync(m->attn_gran, 0, (size_t)(f.n_heads + 2 * f.n_kv_heads) * f.head_size * 8, c->stream); // (tag 0: no launch's)
     (void)hipMemsetAsync(m->kv_vis_dev, 1, nctx, c->stream);
     m->kv_vis_host.assign(nctx, 1);
     m->k_cache.assign(L, nullptr); m->v_cache.assign(L, nullptr);

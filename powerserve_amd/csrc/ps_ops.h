@@ -46,6 +46,7 @@ struct psl_attn_args {
     unsigned *sync;          // [2048] words, zeroed once: [31] the one-launch decode attention's spin-timeout flag
     float *xchg;             // attn_decode2: raw scores in flight between the workgroups of a kv head, [n_kv_heads][4][n_ctx rounded up to 32]; null: not used
     unsigned *tick;          // attn_decode2: [64 * kv head] arrival counters, zeroed once (epoch = ticket / workgroups per head)
+    unsigned long long *gran; // the fused Q / K / V + attention launch: [n_kv_heads][(r2 + 2) * head_size] {tag, value} granules of rendezvous A, zeroed with `tick`; null: the counter hand-off
     int n_kv_lo;             // attn_decode2: a lower bound of pos0 + 1 known to the host at enqueue time (a prefetch HINT only)
     int kv_stream;           // single-token kernels: 1 = the cached K rows / V channels are read with non-temporal loads (the model's whole cache does not fit the memory-side
                              // cache, so nothing of it survives from token to token and it should not displace what does); 0 = plain loads (a small cache is served from there)
