@@ -47,7 +47,6 @@ void ps_rope_table_host(const ps_rope_params *rp, int64_t ne0, const int32_t *po
 }
 
 static inline bool is_quant(int t) { return t == PS_Q4_0 || t == PS_Q8_0 || t == PS_Q4_K || t == PS_Q5_K || t == PS_Q6_K; }
-static inline bool is_row_wave(int t) { return t == PS_Q5_K || t == PS_Q6_K; } // one wave per weight row (k_gemv6.hip)
 
 // ------------------------------------------------------------------ device allocations (ps_internal.h)
 namespace {
@@ -324,39 +323,11 @@ int ps_hip_mul_mat(ps_hip_ctx *c, const ps_tensor *dst, const ps_tensor *src0, c
         if (!w || w->dtype != src0->dtype || w->K != src0->ne[0] || w->N != src0->ne[1]) PS_FAIL(c, "mul_mat: weight handle mismatch");
         const int64_t K = w->K, bs = src1->ne[1] * src1->ne[2] * src1->ne[3];
         if (src1->nb[1] != (uint64_t)K * 4 || dst->nb[1] != (uint64_t)w->N * 4) PS_FAIL(c, "mul_mat: quantized path needs contiguous rows");
-        const int vdt = ps_hip_vec_dot_type(w->dtype);
         if (ensure(c, &c->act_buf, &c->act_cap, ps_act_bytes(K, bs))) return 1;
-        ps_act a = ps_act_carve(c->act_buf, K, bs);
-        if (is_row_wave(w->dtype) && bs == 1) { // single column: producer / chain-wave kernel, quantizer in its prologue (k_gemvk.hip)
-            psk_gemv_args g{};
-            g.n_w = 1; g.w[0] = w; g.out[0] = (float *)dst->data; g.ldo[0] = w->N;
-            g.pro = 2; g.pro_x = (const float *)src1->data;
-            const int rc = psk_gemvk(c->stream, c->n_cu, g, a, K);
-            if (rc == 0) { PS_CHECK(c, hipGetLastError()); return 0; }
-            if (rc != -1) { c->err = "mul_mat: Q5_K / Q6_K mat-vec launch rc=" + std::to_string(rc); return 2; }
-        }
-        if (is_row_wave(w->dtype)) { // one wave per row (k_gemv6.hip)
-            psk_quantize_act(c->stream, vdt, 0, (const float *)src1->data, nullptr, nullptr, 0.f, K, bs, a);
-            psk_gemv6_args g6{w, (float *)dst->data, w->N, nullptr, nullptr};
-            if (int rc = psk_gemv6(c->stream, c->n_cu, g6, a, K, bs)) { c->err = "mul_mat: Q5_K / Q6_K launch rc=" + std::to_string(rc); return 2; }
-            PS_CHECK(c, hipGetLastError());
-            return 0;
-        }
-        if (bs >= 2) { // batches: quantize once, 8 / 16 columns per workgroup (psk_gemm8)
-            psk_quantize_act(c->stream, vdt, 0, (const float *)src1->data, nullptr, nullptr, 0.f, K, bs, a);
-            psk_gemv_args g{};
-            g.n_w = 1; g.w[0] = w; g.out[0] = (float *)dst->data; g.ldo[0] = w->N;
-            const int rc = psk_gemm8(c->stream, c->n_cu, g, a, K, bs);
-            if (rc == 0) { PS_CHECK(c, hipGetLastError()); return 0; }
-            if (rc != -1) { c->err = "mul_mat: gemm launch rc=" + std::to_string(rc); return 2; }
-        }
-        for (int64_t c0 = 0; c0 < bs; c0 += 4) { // <= 4 columns per GEMV launch; activation quantized in its prologue
-            const int64_t nb = bs - c0 < 4 ? bs - c0 : 4;
-            psk_gemv_args g{};
-            g.n_w = 1; g.w[0] = w; g.out[0] = (float *)dst->data + c0 * w->N; g.ldo[0] = w->N;
-            g.pro = 2; g.pro_x = (const float *)src1->data + c0 * K;
-            if (int rc = psk_gemv(c->stream, c->n_cu, g, a, vdt, K, nb)) { c->err = "mul_mat: gemv launch rc=" + std::to_string(rc); return 2; }
-        }
+        psk_gemv_args g{};
+        g.n_w = 1; g.w[0] = w; g.out[0] = (float *)dst->data; g.ldo[0] = w->N;
+        g.pro = 2; g.pro_x = (const float *)src1->data;
+        if (psk_matmul(c, g, psk_mm_scratch{ps_act_carve(c->act_buf, K, bs), nullptr, {nullptr, nullptr}}, K, bs)) PS_FAIL(c, "mul_mat: " + c->err);
     } else if (src0->dtype == PS_F16) {
         // any K: activation rounded to fp16 once, then the 32 fp32 chains + double leftovers of ggml_vec_dot_f16 (k_gemvh.hip)
         const ps_weight *w = (const ps_weight *)src0->data;
@@ -370,7 +341,7 @@ int ps_hip_mul_mat(ps_hip_ctx *c, const ps_tensor *dst, const ps_tensor *src0, c
         psk_gemv_args g{};
         g.n_w = 1; g.w[0] = w; g.out[0] = (float *)dst->data; g.ldo[0] = w->N;
         g.pro = 2; g.pro_x = (const float *)src1->data; // rounded in the launch's prologue (one column) or into act_buf first
-        if (int rc = psk_gemvh(c->stream, c->n_cu, g, (_Float16 *)c->act_buf, K, bs)) { c->err = "mul_mat: F16 launch rc=" + std::to_string(rc); return 2; }
+        if (psk_matmul(c, g, psk_mm_scratch{ps_act{}, (_Float16 *)c->act_buf, {nullptr, nullptr}}, K, bs)) PS_FAIL(c, "mul_mat: " + c->err);
     } else if (src0->dtype == PS_F32) {
         if (src0->nb[0] != 4) PS_FAIL(c, "mul_mat: transposed src0 not supported");
         if (src1->ne[2] % src0->ne[2] || src1->ne[3] % src0->ne[3]) PS_FAIL(c, "mul_mat: src0 not broadcastable");

@@ -1392,8 +1392,7 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
     // arithmetic, needs more than the 168 registers of a twelve-wave workgroup: 30 spills, 12.2 k tok/s.)
     // 8B tree forward, ms by width (profiles/r02_tree_forward_latency_8b.json): 2: 4.7, 8: 4.7, 12: 4.8, 16: 4.8 (narrow kernel),
     // 32: 5.9, 64: 6.3, 128: 8.4 (wide); the round-1 kernels that spread a row group's integer work over producer waves
-    // (gemm8): 2: 4.9, 8: 5.0, 12: 6.1, 16: 6.2, 32: 8.8, 64: 12.8, 96: 19.9.  PS_GEMM4K_MIN_COLS moves the switch (default 2).
-    if (bs < ps_gemm4k_min_cols() || p.nsb % 4) return -1;
+    // (gemm8): 2: 4.9, 8: 5.0, 12: 6.1, 16: 6.2, 32: 8.8, 64: 12.8, 96: 19.9.  PS_GEMM4K_MIN_COLS moves the switch (default 2, psk_gemm4k_frag).
     static const bool no_wav = getenv("PS_NO_GEMM4K_WAV") != nullptr;                                     // (A/B switches for measurements)
     static const int wav_cfg = getenv("PS_GEMM4K_WAV_CFG") ? atoi(getenv("PS_GEMM4K_WAV_CFG")) : 0;
     const int par_cfg = g_g4k_par; // 0: off, 4 / 8: that many waves per tile, else by tile count
@@ -1424,7 +1423,6 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
         (void)hipFuncSetAttribute((const void *)gemm4k_narrow_kernel<0, 1, PS_Q5_K>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
     }
     if (p.wt == PS_Q5_K) { // (single matrix, EPI 0)
-        if (epi != 0) return -1;
         if (ctw == 1) { psk_note_kernel("gemm4k_narrow_kernel<0, 1, 13>"); hipLaunchKernelGGL((gemm4k_narrow_kernel<0, 1, PS_Q5_K>), grid, blkn, LDS1, st, p); }
         else { psk_note_kernel("gemm4k_kernel<0, 13>"); hipLaunchKernelGGL((gemm4k_kernel<0, PS_Q5_K>), grid, blk, G4K_LDS, st, p); }
     } else if (ctw == 1 && n_ct == 1 && !no_wav && epi != 1 && par_cfg != 0 && !(2 * p.n_tasks >= 4 * n_cu || wav_cfg == 1)) {
@@ -1458,20 +1456,24 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
     return 0;
 }
 
-// Q4_K batched mat-mul from fragment-major Q8_K activations (act.qf).  -1: not covered (the caller takes gemm8m).
-int psk_gemm4k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
+// Q4_K batched mat-mul from fragment-major Q8_K activations (act.qf).  With a.rope (a Q / K / V batch of at most 16 columns: the narrow
+// kernel) the epilogue rotates and appends to the KV cache: 8B tree forward 12 wide 4.72 -> 4.62 ms.
+bool psk_gemm4k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
     static const bool off = getenv("PS_NO_GEMM4K") != nullptr; // (A/B switch for measurements)
-    if (off || a.pro != 0 || a.n_w < 1 || !act.qf || K % 256) return -1;
-    if (a.rope && (a.n_w != 3 || a.silu_pair || a.residual || bs > 16)) return -1;
+    if (off || a.pro != 0 || a.n_w < 1 || !psk_gemm4k_frag(K, bs)) return false;
+    if (a.rope && (a.n_w != 3 || a.silu_pair || a.residual || bs > 16)) return false;
+    for (int i = 0; i < a.n_w; i++)
+        if (a.w[i]->dtype != PS_Q4_K || a.w[i]->K != K || a.w[i]->N % 32 || a.ldo[i] % 4) return false;
+    return !a.silu_pair || (a.n_w == 2 && a.w[0]->N == a.w[1]->N && a.ldo[0] == a.ldo[1]);
+}
+int psk_gemm4k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
     G4KParams p{};
     int pairs_total = 0;
     for (int i = 0; i < a.n_w; i++) {
-        if (a.w[i]->dtype != PS_Q4_K || a.w[i]->K != K || a.w[i]->N % 32 || a.ldo[i] % 4) return -1;
         p.w[i] = G4KMat{a.w[i]->qs, a.w[i]->aux, nullptr, a.out[i], a.bias[i], a.w[i]->N, a.ldo[i], (int)(a.w[i]->N / 16)};
         pairs_total += p.w[i].n_tiles / 2;
     }
     const int epi = a.silu_pair ? 1 : 0;
-    if (epi == 1 && (a.n_w != 2 || a.w[0]->N != a.w[1]->N || a.ldo[0] != a.ldo[1])) return -1;
     p.n_w = a.n_w; p.nsb = (int)(K / 256); p.bs = (int)bs;
     p.n_tasks = epi == 1 ? p.w[0].n_tiles : pairs_total;
     p.residual = a.residual; p.qf = act.qf; p.mf = act.mf;
@@ -1481,27 +1483,33 @@ int psk_gemm4k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int
     return g4k_launch(st, n_cu, p, epi, bs);
 }
 
-// Q5_K (single matrix, the Q5_K_M mix): the same kernels with the Q5_K producer.  -1: not covered.
-int psk_gemm5k(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int64_t K, int64_t bs) {
+// Q5_K (single matrix, the Q5_K_M mix): the same kernels with the Q5_K producer.
+bool psk_gemm5k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
     static const bool off = getenv("PS_NO_GEMM5K") != nullptr; // (A/B switch for measurements)
-    const ps_weight *w = a.w;
-    if (off || !w || w->dtype != PS_Q5_K || w->K != K || K % 1024 || w->N % 32 || a.ldo % 4 || !act.qf) return -1;
+    const ps_weight *w = a.w[0];
+    return !off && a.n_w == 1 && !a.silu_pair && w->dtype == PS_Q5_K && w->K == K && w->N % 32 == 0 && a.ldo[0] % 4 == 0 && psk_gemm4k_frag(K, bs);
+}
+int psk_gemm5k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
+    const ps_weight *w = a.w[0];
     G4KParams p{};
-    p.w[0] = G4KMat{w->qs, w->sc, w->qh, a.out, a.bias, w->N, a.ldo, (int)(w->N / 16)};
+    p.w[0] = G4KMat{w->qs, w->sc, w->qh, a.out[0], a.bias[0], w->N, a.ldo[0], (int)(w->N / 16)};
     p.n_w = 1; p.nsb = (int)(K / 256); p.bs = (int)bs; p.n_tasks = p.w[0].n_tiles / 2;
     p.residual = a.residual; p.qf = act.qf; p.mf = act.mf; p.dbg = nullptr; p.wt = PS_Q5_K;
     return g4k_launch(st, n_cu, p, 0, bs);
 }
 
-// Q6_K batched mat-mul from the same fragment-major activations.  -1: not covered (the caller keeps the 8-column mat-vec launches).
-int psk_gemm6k(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int64_t K, int64_t bs) {
+// Q6_K batched mat-mul from the same fragment-major activations (narrower batches keep the 8-column mat-vec launches).
+bool psk_gemm6k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
     static const bool off = getenv("PS_NO_GEMM6K") != nullptr; // (A/B switch for measurements)
-    const ps_weight *w = a.w;
     static const int64_t min_cols = [] { const char *e = getenv("PS_GEMM6K_MIN_COLS"); return e ? (int64_t)atoll(e) : (int64_t)9; }(); // (8B Q4_K_M tree forward, ms, threshold 17 / 9 / 2: 8 wide 5.9 / 6.0 / 6.2, 12: 6.9 / 6.3 / 6.3, 16: 7.6 / 6.4 / 6.3)
-    if (off || !w || w->dtype != PS_Q6_K || w->K != K || K % 1024 || w->N % 32 || a.ldo % 2 || !act.qf || bs < min_cols || bs < ps_gemm4k_min_cols()) return -1;
+    const ps_weight *w = a.w[0];
+    return !off && a.n_w == 1 && !a.silu_pair && w->dtype == PS_Q6_K && w->K == K && w->N % 32 == 0 && a.ldo[0] % 2 == 0 && bs >= min_cols && psk_gemm4k_frag(K, bs);
+}
+int psk_gemm6k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
+    const ps_weight *w = a.w[0];
     G6KParams p{};
     p.ql = w->qs; p.qh = w->qh; p.sc = (const int8_t *)w->sc; p.d = (const uint16_t *)w->aux;
-    p.out = a.out; p.bias = a.bias; p.residual = a.residual; p.N = w->N; p.ldo = a.ldo;
+    p.out = a.out[0]; p.bias = a.bias[0]; p.residual = a.residual; p.N = w->N; p.ldo = a.ldo[0];
     p.nsb = (int)(K / 256); p.bs = (int)bs; p.n_tasks = (int)(w->N / 32);
     p.qf = act.qf; p.mf = act.mf;
     const int n_ct = (int)((bs + 15) / 16);
@@ -1514,14 +1522,4 @@ int psk_gemm6k(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, in
     psk_note_kernel("gemm6k_kernel");
     hipLaunchKernelGGL(gemm6k_kernel, dim3((unsigned)n_wg), dim3((G4K_NC + G4K_NP) * 64), G6K_LDS, st, p);
     return 0;
-}
-
-// Whether psk_gemm4k(a with a.rope set) will take a Q / K / V launch of `bs` columns AND do RoPE + the KV append in its epilogue
-// (tree verify, prompt tails; mirrors the checks of psk_gemm4k and g4k_launch): 8B tree forward 12 wide 4.72 -> 4.62 ms.
-bool psk_gemm4k_rope_ok(const psk_gemv_args &a, int64_t K, int64_t bs) {
-    static const bool off = getenv("PS_NO_GEMM4K") != nullptr || getenv("PS_NO_ROPE_FUSION") != nullptr;
-    if (off || a.n_w != 3 || a.silu_pair || a.residual || K % 1024 || bs < 2 || bs < ps_gemm4k_min_cols() || bs > 16) return false; // (at most 16 columns: the narrow kernel)
-    for (int i = 0; i < 3; i++)
-        if (!a.w[i] || a.w[i]->dtype != PS_Q4_K || a.w[i]->K != K || a.w[i]->N % 32 || a.ldo[i] % 4) return false;
-    return true;
 }

@@ -45,8 +45,6 @@ struct GemvParams {
     const float *ad;
     const int16_t *abs16;
     unsigned long long *dbg; // timeline buffer or null (ps_hip_debug_timeline)
-    int split_q, split_r;    // (unused by the kernels of this file since gemv3 went)
-    psk_rope_kv rope;        // EPI 2
 };
 
 // EPI 0: out = y (+bias) (+residual).   EPI 1: out[0] = silu(y_w0) * y_w1 (same row of w[0] and w[1]).
@@ -475,11 +473,9 @@ int launch_epi(hipStream_t st, int n_cu, const GemvParams &p, int epi, int pro) 
 
 template <int WT>
 int launch_wt(hipStream_t st, int n_cu, const GemvParams &p, int epi, int pro) {
-    if (epi == 2) return 8; // the fused RoPE epilogue exists in the producer / chain-wave kernels only (psk_gemv_rope_ok)
     if (p.bs == 1 && launch_g1_wt<WT>(st, n_cu, p, epi, pro)) return 0;
     if (p.bs == 1) return launch_epi<WT, 1>(st, n_cu, p, epi, pro);
-    if (p.bs <= 4) return launch_epi<WT, 4>(st, n_cu, p, epi, pro);
-    return 3;
+    return launch_epi<WT, 4>(st, n_cu, p, epi, pro);
 }
 
 // Activation image of 8 / 16 pre-quantized columns in LDS, shared by gemm8m_kernel and gemm8b_kernel.
@@ -877,12 +873,6 @@ unsigned long long *psk_gemv_dbg_buf(int epi, int pro) { // key = k1 + 100 * (k2
     return nullptr;
 }
 
-bool psk_gemv_rope_ok(int wt, int64_t K) { // a Q / K / V launch of ONE type whose epilogue rotates and appends: mirrors psk_gemv4 / psk_gemvb / psk_gemvk
-    if (wt == PS_Q4_K) return psk_gemv4_covers(K);
-    if (psk_gemvb_covers(wt, K)) return true;
-    return wt == PS_Q5_K && psk_gemvk_covers(wt, K); // (Q / K / V all Q5_K: k_gemvk.hip)
-}
-
 size_t psk_gemv_lds_col_bytes(int wt, int64_t K) {
     const int64_t blk = (wt == PS_Q4_K) ? 256 : 32, unit = (wt == PS_Q4_K) ? 256 : 128;
     const int64_t Kp = (K + unit - 1) / unit * unit;
@@ -890,8 +880,7 @@ size_t psk_gemv_lds_col_bytes(int wt, int64_t K) {
     return (b + 15) / 16 * 16;
 }
 
-// Batched mat-mul from pre-quantized activations; returns -1 when the shape is not covered (caller falls back to
-// column groups through the mat-vec).
+// Batched mat-mul from pre-quantized activations (Q4_K rows that psk_gemm4k_takes declines, Q4_0 / Q8_0 batches).
 template <int EPI, int NWV, int C>
 static void launch_gemm8m_k(hipStream_t st, const GemvParams &p, const dim3 grid, size_t smem) {
     static unsigned long long attr = 0; // devices that have the attribute
@@ -919,31 +908,29 @@ static int launch_gemm8(hipStream_t st, const GemvParams &p, int epi, int nwv, c
     }
     return 0;
 }
-int psk_gemm8(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
-    if (a.pro != 0 || a.n_w < 1) return -1;
-    if (a.rope && !(a.w[0]->dtype == PS_Q4_K && bs >= 2)) return -1;
-    if (a.w[0]->dtype == PS_Q4_K) { // prefill chunks: fp16 matrix cores on exact integers, producer / consumer waves (k_gemm4k.hip)
-        const int rc = psk_gemm4k(st, n_cu, a, act, K, bs);
-        if (rc != -1) return rc;
-    }
-    if (a.rope) return 3; // (a batch with the RoPE epilogue requested that the chunk mat-mul did not take: psk_gemm4k_rope_ok and psk_gemm4k disagree)
+static int64_t gemm8_lds(int wt, int64_t K) { return K / (wt == PS_Q4_K ? 256 : 128) * 8 * (wt == PS_Q4_K ? 304 : 144); } // [unit][column] records (gemm8_stage)
+bool psk_gemm8_takes(const psk_gemv_args &a, int64_t K, int64_t /*bs*/) {
+    if (a.pro != 0 || a.n_w < 1 || a.rope) return false;
     const int wt = a.w[0]->dtype;
-    if (wt != PS_Q4_K && wt != PS_Q8_0 && wt != PS_Q4_0) return -1;
-    const int64_t unit = wt == PS_Q4_K ? 256 : 128, blk = wt == PS_Q4_K ? 256 : 32, rg = wt == PS_Q4_0 ? 16 : 8;
-    if (K % unit) return -1;
+    if ((wt != PS_Q4_K && wt != PS_Q8_0 && wt != PS_Q4_0) || K % (wt == PS_Q4_K ? 256 : 128)) return false;
+    for (int i = 0; i < a.n_w; i++)
+        if (a.w[i]->dtype != wt || a.w[i]->K != K) return false;
+    if (a.silu_pair && (a.n_w != 2 || a.w[0]->N != a.w[1]->N)) return false;
+    return gemm8_lds(wt, K) <= 158 * 1024;
+}
+int psk_gemm8(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
+    const int wt = a.w[0]->dtype;
+    const int64_t rg = wt == PS_Q4_0 ? 16 : 8;
     GemvParams p{};
     p.n_w = a.n_w; p.K = K; p.bs = bs; p.residual = a.residual;
     p.aq = act.qs; p.ad = act.d; p.abs16 = act.bs16;
     for (int i = 0; i < a.n_w; i++) {
-        if (a.w[i]->dtype != wt || a.w[i]->K != K) return -1;
         const int64_t ng = (a.w[i]->N + rg - 1) / rg;
         p.w[i] = GemvW{a.w[i]->qs, a.w[i]->aux, a.out[i], a.bias[i], a.w[i]->N, a.ldo[i], ng};
         p.groups_total += ng;
     }
     const int epi = a.silu_pair ? 1 : 0;
-    if (epi == 1 && (a.n_w != 2 || a.w[0]->N != a.w[1]->N)) return -1;
-    const size_t smem = (size_t)(K / unit) * 8 * (wt == PS_Q4_K ? 304 : 144); // [unit][column] records (gemm8_stage)
-    if (smem > 158 * 1024) return -1;
+    const size_t smem = (size_t)gemm8_lds(wt, K);
     const int64_t n_tasks = epi == 1 ? p.w[0].n_groups : p.groups_total;
     // one wave per row group; 16-wave workgroups amortise the LDS staging of the 8 columns, 4-wave workgroups spread a
     // small launch (tree verify, short prefill tails) over all CUs
@@ -963,58 +950,34 @@ int psk_gemm8(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int6
     }
 }
 
-// up to psk_gemv_max_cols columns per launch (more than 4 only from pre-quantized activations); larger batches are
-// split by the caller.
-int psk_gemv_max_cols(int wt, int64_t K) {
-    const size_t cb = psk_gemv_lds_col_bytes(wt, K);
-    (void)cb;
-    return 4; // (the 8-column instantiations of the in-lane kernel measured slower than 4; batches take psk_gemm8)
+// 1..4 columns per launch (the 8-column instantiations of the in-lane kernel measured slower than 4; batches take psk_gemm8): the
+// single-column shapes that gemv4 / gemvb do not take, and the column groups of a batch that the batched mat-muls decline
+bool psk_gemv_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
+    if (bs < 1 || bs > 4 || a.n_w < 1 || a.n_w > 3 || a.rope) return false;
+    const int wt = a.w[0]->dtype;
+    if (wt != PS_Q4_0 && wt != PS_Q8_0 && wt != PS_Q4_K) return false;
+    for (int i = 0; i < a.n_w; i++)
+        if (a.w[i]->dtype != wt || a.w[i]->K != K) return false;
+    if (a.silu_pair && (a.n_w != 2 || a.w[0]->N != a.w[1]->N)) return false;
+    return psk_gemv_lds_col_bytes(wt, K) * (bs == 1 ? 1 : 4) <= 158 * 1024;
 }
 
-int psk_gemv(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int vdt, int64_t K, int64_t bs) {
+int psk_gemv(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
+    const int wt = a.w[0]->dtype, rg = wt == PS_Q4_0 ? 16 : 8;
     GemvParams p{};
-    p.n_w          = a.n_w;
-    p.groups_total = 0;
-    p.K            = K;
-    p.bs           = bs;
-    p.residual     = a.residual;
-    p.x            = a.pro_x;
-    p.nw           = a.pro_norm_w;
-    p.eps          = a.pro_eps;
-    p.aq           = act.qs;
-    p.ad           = act.d;
-    p.abs16        = act.bs16;
-    const int wt   = a.w[0]->dtype;
-    const int rg   = (wt == PS_Q4_0) ? 16 : 8;
+    p.n_w = a.n_w; p.K = K; p.bs = bs; p.residual = a.residual;
+    p.x = a.pro_x; p.nw = a.pro_norm_w; p.eps = a.pro_eps;
+    p.aq = act.qs; p.ad = act.d; p.abs16 = act.bs16;
     for (int i = 0; i < a.n_w; i++) {
-        if (a.w[i]->dtype != wt || a.w[i]->K != K) return 4;
         const int64_t ng = (a.w[i]->N + rg - 1) / rg;
         p.w[i] = GemvW{a.w[i]->qs, a.w[i]->aux, a.out[i], a.bias[i], a.w[i]->N, a.ldo[i], ng};
         p.groups_total += ng;
     }
-    (void)vdt;
     p.col_bytes = (int64_t)psk_gemv_lds_col_bytes(wt, K);
-    if ((size_t)p.col_bytes * (bs == 1 ? 1 : 4) > 158 * 1024) return 7;
-    const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0);
-    const bool rope_part = a.rope && (a.n_w != 3 || a.rope_wi0 != 0); // a part of the Q / K / V triple: gemv4 only
-    if (a.rope) {
-        if (a.n_w + a.rope_wi0 > 3 || bs != 1 || a.pro != 1) return 9;
-        p.rope = *a.rope;
-    }
-    if (epi == 1 && (a.n_w != 2 || a.w[0]->N != a.w[1]->N)) return 5;
-    if (bs == 1 && wt == PS_Q4_K) { // second-generation decode kernel (k_gemv4.hip)
-        const int rc = psk_gemv4(st, n_cu, a, act, K);
-        if (rc != -1) return rc;
-    }
-    if (rope_part) return 9;
-    if (bs == 1 && (wt == PS_Q4_0 || wt == PS_Q8_0)) { // producer / chain-wave kernel of the 32-element block formats (k_gemvb.hip)
-        const int rc = psk_gemvb(st, n_cu, a, act, K);
-        if (rc != -1) return rc;
-    }
+    const int epi = a.silu_pair ? 1 : 0;
     switch (wt) {
     case PS_Q4_0: return launch_wt<PS_Q4_0>(st, n_cu, p, epi, a.pro);
     case PS_Q8_0: return launch_wt<PS_Q8_0>(st, n_cu, p, epi, a.pro);
-    case PS_Q4_K: return launch_wt<PS_Q4_K>(st, n_cu, p, epi, a.pro);
+    default: return launch_wt<PS_Q4_K>(st, n_cu, p, epi, a.pro);
     }
-    return 6;
 }

@@ -431,11 +431,10 @@ void launch_g4(hipStream_t st, int grid, const G4Params &p) {
 template <int NW, int DC, int XW, int KC, int YS = 0>
 int launch_g4_ep(hipStream_t st, int grid, const G4Params &p, int epi, int pro) {
     constexpr int TPW = ((16 << KC) + NW - 1) / NW;
-    if (epi == 2) { if (pro != 1) return -1; launch_g4<NW, DC, TPW, XW, 2, 1, YS>(st, grid, p); return 0; }
+    if (epi == 2) { launch_g4<NW, DC, TPW, XW, 2, 1, YS>(st, grid, p); return 0; }
     if (epi == 1) {
         if (pro == 1) launch_g4<NW, DC, TPW, XW, 1, 1, YS>(st, grid, p);
-        else if (pro == 0) launch_g4<NW, DC, TPW, XW, 1, 0, YS>(st, grid, p);
-        else return -1;
+        else launch_g4<NW, DC, TPW, XW, 1, 0, YS>(st, grid, p);
         return 0;
     }
     if (pro == 0) launch_g4<NW, DC, TPW, XW, 0, 0, YS>(st, grid, p);
@@ -446,8 +445,7 @@ int launch_g4_ep(hipStream_t st, int grid, const G4Params &p, int epi, int pro) 
 template <int NW, int DC, int XW, int YS = 0>
 int launch_g4_kc(hipStream_t st, int grid, const G4Params &p, int epi, int pro) {
     if (p.n_units <= 16) return launch_g4_ep<NW, DC, XW, 0, YS>(st, grid, p, epi, pro);
-    if (p.n_units <= 64) return launch_g4_ep<NW, DC, XW, 2, YS>(st, grid, p, epi, pro);
-    return -1;
+    return launch_g4_ep<NW, DC, XW, 2, YS>(st, grid, p, epi, pro); // (n_units <= 64: psk_gemv4_takes)
 }
 
 } // namespace
@@ -455,35 +453,32 @@ int launch_g4_kc(hipStream_t st, int grid, const G4Params &p, int epi, int pro) 
 int g_g4_cfg = getenv("PS_G4_CFG") ? atoi(getenv("PS_G4_CFG")) : 0; // ps_hip_debug_set(1, cfg)  (cfg 20..23 were round 4's LDS-DMA kernel: tools/experiments/r04_k_gemv7.hip)
 int g_g4_flags = 0; // ps_hip_debug_set(2, flags): reserved for what-if switches
 
-bool psk_gemv4_covers(int64_t K) { // rows end on multiples of four units
+bool psk_gemv4_takes(const psk_gemv_args &a, int64_t K, int64_t bs) { // rows end on multiples of four units
     static const bool off = getenv("PS_NO_GEMV4") != nullptr; // (A/B switch for measurements)
-    return !off && K % 1024 == 0 && K <= 16384;
+    if (off || bs != 1 || a.n_w < 1 || a.n_w > 3 || K % 1024 || K > 16384) return false;
+    for (int i = 0; i < a.n_w; i++)
+        if (a.w[i]->dtype != PS_Q4_K || a.w[i]->K != K || a.w[i]->N < 1) return false;
+    if (a.silu_pair) return a.n_w == 2 && a.w[0]->N == a.w[1]->N && a.pro != 2; // (the SiLU pair has no plain-quantizer prologue)
+    return !a.rope || (a.rope_wi0 >= 0 && a.n_w + a.rope_wi0 <= 3 && a.pro == 1);
 }
 
-// Single-column Q4_K mat-vec.  Returns -1 when the launch is not covered (the caller falls back to gemv1 / gemv_kernel).
+// Single-column Q4_K mat-vec (psk_gemv4_takes).
 int psk_gemv4(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K) {
-    if (a.n_w < 1 || a.n_w > 3 || !psk_gemv4_covers(K)) return -1;
     G4Params p{};
     int groups_total = 0;
     for (int i = 0; i < a.n_w; i++) {
-        if (a.w[i]->dtype != PS_Q4_K || a.w[i]->K != K) return -1;
         const int ng = (int)((a.w[i]->N + 7) / 8);
         p.w[i] = G4Mat{a.w[i]->qs, a.w[i]->aux, a.out[i], a.bias[i], a.w[i]->N, ng};
         groups_total += ng;
     }
     const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0);
-    if (epi == 1 && (a.n_w != 2 || a.w[0]->N != a.w[1]->N)) return -1;
-    if (epi == 2) {
-        if (a.n_w + a.rope_wi0 > 3 || a.rope_wi0 < 0 || a.pro != 1) return -1;
-        p.rope = *a.rope; p.rope_wi0 = a.rope_wi0;
-    }
+    if (epi == 2) { p.rope = *a.rope; p.rope_wi0 = a.rope_wi0; }
     p.n_w = a.n_w; p.n_units = (int)(K / 256); p.K = (int)K;
     p.n_tasks = epi == 1 ? p.w[0].n_groups : groups_total;
     p.residual = a.residual; p.x = a.pro_x; p.nw = a.pro_norm_w; p.eps = a.pro_eps;
     p.aq = act.qs; p.ad = act.d; p.abs16 = act.bs16;
     p.col_bytes = (int)psk_gemv_lds_col_bytes(PS_Q4_K, K);
-    int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
-    if (grid < 1) return -1;
+    const int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
     p.split_q = p.n_tasks / grid; p.split_r = p.n_tasks % grid;
     p.dbg = psk_gemv_dbg_buf(epi, (epi == 0 && a.pro == 2 && K <= a.w[0]->N) ? 3 : a.pro); // timeline keys: 9 QKV, 3 O (K <= N), 5 gate/up, 2 down
     // wave configuration (measured, tools/g4_variants.py): rows of a multiple of 7 units take 7 (14) producers

@@ -219,55 +219,24 @@ __global__ __launch_bounds__(256) void gemv5_kernel(Gemv5Params p) {
     }
 }
 
-int launch_gemv5(hipStream_t st, int n_cu, const psk_gemv6_args *a, int n_w, ps_act act, int64_t K, int64_t bs) {
-    Gemv5Params p{};
-    p.n_w = n_w; p.K = K; p.nsb = (int)(K / 256);
-    for (int i = 0; i < n_w; i++) p.N += a[i].w->N;
-    const int64_t nwg = (p.N + 3) / 4;
-    const unsigned grid = (unsigned)(nwg < (int64_t)n_cu * 16 ? nwg : (int64_t)n_cu * 16);
-    for (int64_t c0 = 0; c0 < bs; c0 += 8) {
-        const int nc = (int)(bs - c0 < 8 ? bs - c0 : 8);
-        p.aq = act.qs + c0 * K; p.ad = act.d + c0 * (K / 256); p.abs16 = act.bs16 + c0 * (K / 16);
-        for (int i = 0; i < n_w; i++) {
-            const ps_weight *w = a[i].w;
-            p.w[i] = Gemv5Mat{w->qs, w->qh, (const uint4 *)w->sc, w->N, a[i].ldo, a[i].out + c0 * a[i].ldo, a[i].bias,
-                              a[i].residual ? a[i].residual + c0 * a[i].ldo : nullptr};
-        }
-        p.nc = nc;
-        if (nc == 1) { psk_note_kernel("gemv5_kernel<1>"); hipLaunchKernelGGL(gemv5_kernel<1>, dim3(grid), dim3(256), 0, st, p); }
-        else if (nc == 2) { psk_note_kernel("gemv5_kernel<2>"); hipLaunchKernelGGL(gemv5_kernel<2>, dim3(grid), dim3(256), 0, st, p); }
-        else if (nc <= 4) { psk_note_kernel("gemv5_kernel<4>"); hipLaunchKernelGGL(gemv5_kernel<4>, dim3(grid), dim3(256), 0, st, p); }
-        else { psk_note_kernel("gemv5_kernel<8>"); hipLaunchKernelGGL(gemv5_kernel<8>, dim3(grid), dim3(256), 0, st, p); }
-    }
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-
 } // namespace
 
-int psk_gemv6(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int64_t K, int64_t bs) {
-    const ps_weight *w = a.w;
-    if (w->dtype == PS_Q5_K && w->K == K && K % 256 == 0) {
-        if (bs >= ps_gemm4k_min_cols()) { // batches: the matrix-core mat-mul with the Q5_K producer (k_gemm4k.hip)
-            const int rc = psk_gemm5k(st, n_cu, a, act, K, bs);
-            if (rc != -1) return rc;
-        }
-        return launch_gemv5(st, n_cu, &a, 1, act, K, bs);
-    }
-    if (w->dtype != PS_Q6_K || w->K != K || K % 256) return 4;
-    { // chunks and wide trees: the matrix-core mat-mul (k_gemm4k.hip)
-        const int rc = psk_gemm6k(st, n_cu, a, act, K, bs);
-        if (rc != -1) return rc;
-    }
+// Q6_K: one matrix, any number of columns (groups of 8)
+bool psk_gemv6_takes(const psk_gemv_args &a, int64_t K, int64_t /*bs*/) {
+    return a.n_w == 1 && !a.silu_pair && a.w[0]->dtype == PS_Q6_K && a.w[0]->K == K && K % 256 == 0;
+}
+int psk_gemv6(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
+    const ps_weight *w = a.w[0];
     Gemv6Params p{};
     p.ql = w->qs; p.qh = w->qh; p.sc = w->sc; p.d = (const uint16_t *)w->aux;
     p.K = K; p.N = w->N; p.nsb = (int)(K / 256);
-    p.ldo = a.ldo; p.bias = a.bias;
+    p.ldo = a.ldo[0]; p.bias = a.bias[0];
     const int64_t nwg = (w->N + 3) / 4;
     const unsigned grid = (unsigned)(nwg < (int64_t)n_cu * 16 ? nwg : (int64_t)n_cu * 16);
     for (int64_t c0 = 0; c0 < bs; c0 += 8) {
         const int nc = (int)(bs - c0 < 8 ? bs - c0 : 8);
         p.aq = act.qs + c0 * K; p.ad = act.d + c0 * (K / 256);
-        p.out = a.out + c0 * a.ldo; p.residual = a.residual ? a.residual + c0 * a.ldo : nullptr; p.nc = nc;
+        p.out = a.out[0] + c0 * p.ldo; p.residual = a.residual ? a.residual + c0 * p.ldo : nullptr; p.nc = nc;
         if (nc == 1) { psk_note_kernel("gemv6_kernel<1>"); hipLaunchKernelGGL(gemv6_kernel<1>, dim3(grid), dim3(256), 0, st, p); }
         else if (nc == 2) { psk_note_kernel("gemv6_kernel<2>"); hipLaunchKernelGGL(gemv6_kernel<2>, dim3(grid), dim3(256), 0, st, p); }
         else if (nc <= 4) { psk_note_kernel("gemv6_kernel<4>"); hipLaunchKernelGGL(gemv6_kernel<4>, dim3(grid), dim3(256), 0, st, p); }
@@ -276,11 +245,33 @@ int psk_gemv6(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-// Q5_K matrices that share one activation (Q / K / V, gate / up) in ONE launch: single tokens and batches the chunk kernels do
-// not take.  4: not all Q5_K of this K.
-int psk_gemv5_multi(hipStream_t st, int n_cu, const psk_gemv6_args *a, int n_w, ps_act act, int64_t K, int64_t bs) {
-    if (n_w < 1 || n_w > 3 || K % 256) return 4;
-    for (int i = 0; i < n_w; i++)
-        if (!a[i].w || a[i].w->dtype != PS_Q5_K || a[i].w->K != K) return 4;
-    return launch_gemv5(st, n_cu, a, n_w, act, K, bs);
+// Q5_K matrices that share one activation (Q / K / V, gate / up) in ONE launch per 8 columns: single tokens and the batches the chunk
+// kernels do not take.  The residual goes to w[0]'s rows.
+bool psk_gemv5_takes(const psk_gemv_args &a, int64_t K, int64_t /*bs*/) {
+    if (a.n_w < 1 || a.n_w > 3 || a.silu_pair || K % 256) return false;
+    for (int i = 0; i < a.n_w; i++)
+        if (a.w[i]->dtype != PS_Q5_K || a.w[i]->K != K) return false;
+    return true;
+}
+int psk_gemv5(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
+    Gemv5Params p{};
+    p.n_w = a.n_w; p.K = K; p.nsb = (int)(K / 256);
+    for (int i = 0; i < a.n_w; i++) p.N += a.w[i]->N;
+    const int64_t nwg = (p.N + 3) / 4;
+    const unsigned grid = (unsigned)(nwg < (int64_t)n_cu * 16 ? nwg : (int64_t)n_cu * 16);
+    for (int64_t c0 = 0; c0 < bs; c0 += 8) {
+        const int nc = (int)(bs - c0 < 8 ? bs - c0 : 8);
+        p.aq = act.qs + c0 * K; p.ad = act.d + c0 * (K / 256); p.abs16 = act.bs16 + c0 * (K / 16);
+        for (int i = 0; i < a.n_w; i++) {
+            const ps_weight *w = a.w[i];
+            p.w[i] = Gemv5Mat{w->qs, w->qh, (const uint4 *)w->sc, w->N, a.ldo[i], a.out[i] + c0 * a.ldo[i], a.bias[i],
+                              (i == 0 && a.residual) ? a.residual + c0 * a.ldo[0] : nullptr};
+        }
+        p.nc = nc;
+        if (nc == 1) { psk_note_kernel("gemv5_kernel<1>"); hipLaunchKernelGGL(gemv5_kernel<1>, dim3(grid), dim3(256), 0, st, p); }
+        else if (nc == 2) { psk_note_kernel("gemv5_kernel<2>"); hipLaunchKernelGGL(gemv5_kernel<2>, dim3(grid), dim3(256), 0, st, p); }
+        else if (nc <= 4) { psk_note_kernel("gemv5_kernel<4>"); hipLaunchKernelGGL(gemv5_kernel<4>, dim3(grid), dim3(256), 0, st, p); }
+        else { psk_note_kernel("gemv5_kernel<8>"); hipLaunchKernelGGL(gemv5_kernel<8>, dim3(grid), dim3(256), 0, st, p); }
+    }
+    return hipGetLastError() == hipSuccess ? 0 : 1;
 }

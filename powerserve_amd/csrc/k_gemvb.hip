@@ -390,8 +390,8 @@ void launch_gb(hipStream_t st, int grid, const GBParams &p) {
 template <int WT, int TPW>
 int launch_gb_ep(hipStream_t st, int grid, const GBParams &p, int epi, int pro) {
     constexpr int NW = 8;
-    if (epi == 2) { if (pro != 1) return -1; launch_gb<WT, NW, TPW, 2, 1>(st, grid, p); return 0; }
-    if (epi == 1) { if (pro != 1) return -1; launch_gb<WT, NW, TPW, 1, 1>(st, grid, p); return 0; }
+    if (epi == 2) { launch_gb<WT, NW, TPW, 2, 1>(st, grid, p); return 0; }
+    if (epi == 1) { launch_gb<WT, NW, TPW, 1, 1>(st, grid, p); return 0; }
     if (pro == 0) launch_gb<WT, NW, TPW, 0, 0>(st, grid, p);
     else if (pro == 1) launch_gb<WT, NW, TPW, 0, 1>(st, grid, p);
     else launch_gb<WT, NW, TPW, 0, 2>(st, grid, p);
@@ -403,55 +403,51 @@ int launch_gb_wt(hipStream_t st, int grid, const GBParams &p, int epi, int pro) 
     if (tiles <= 8) return launch_gb_ep<WT, 1>(st, grid, p, epi, pro);
     if (tiles <= 16) return launch_gb_ep<WT, 2>(st, grid, p, epi, pro);
     if (tiles <= 32) return launch_gb_ep<WT, 4>(st, grid, p, epi, pro);
-    if (tiles <= 64) return launch_gb_ep<WT, 8>(st, grid, p, epi, pro);
-    return -1;
+    return launch_gb_ep<WT, 8>(st, grid, p, epi, pro); // (tiles <= 64: psk_gemvb_takes)
 }
 
 } // namespace
 
-// row lengths / weight types the kernel takes (psk_gemv_rope_ok asks before the model plans a fused QKV launch)
-bool psk_gemvb_covers(int wt, int64_t K) {
-    static const bool off = getenv("PS_NO_GEMVB") != nullptr; // (A/B switch for measurements)
-    return !off && (wt == PS_Q4_0 || wt == PS_Q8_0) && K >= 128 && K % 128 == 0 && K <= 16384;
+static int gb_tasks(const psk_gemv_args &a) { // row groups (a SiLU pair: of w[0], a group takes the same rows of both)
+    int n = 0;
+    for (int i = 0; i < (a.silu_pair ? 1 : a.n_w); i++) n += (int)((a.w[i]->N + ps_w_rg(a.w[i]->dtype) - 1) / ps_w_rg(a.w[i]->dtype));
+    return n;
 }
 
-// Single-column Q4_0 / Q8_0 mat-vec.  Returns -1 when the launch is not covered (the caller falls back to gemv1 / gemv_kernel).
-int psk_gemvb(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K) {
-    if (a.n_w < 1 || a.n_w > 3) return -1;
+// Q4_0 / Q8_0 single columns.  Measured per launch (profiles/r03_decode_kernel_stats_{1b_q4_0,05b_q8_0}*.txt), this kernel against the register-resident
+// gemv1 (k_gemv.hip), us: rows of 16+ units 1B QKV 6.8 / 10.7, O 5.7 / 6.2, gate/up 8.7 / 11.7, down 8.0 / 12.3; 0.5B gate/up
+// (2 x 7 units) 7.5 / 7.8, down (38) 6.5 / 7.9 -- but rows of 7 units (0.5B QKV 5.4 / 4.6, O 5.7 / 5.4: half a chunk per
+// workgroup, gemv1's 256-thread workgroups start faster) and the long single-matrix stream of the lm_head (1B 40.5 / 37.8,
+// 0.5B 48 / 41: the one LDS pipe of a workgroup carries three record float4s per unit both ways) go to gemv1.
+bool psk_gemvb_takes(const psk_gemv_args &a, int64_t K, int64_t bs, int n_cu) {
+    static const bool off = getenv("PS_NO_GEMVB") != nullptr; // (A/B switch for measurements)
+    if (off || bs != 1 || a.n_w < 1 || a.n_w > 3) return false;
     const int wt = a.w[0]->dtype;
-    if (!psk_gemvb_covers(wt, K)) return -1;
-    const int rg = wt == PS_Q4_0 ? 16 : 8;
+    if ((wt != PS_Q4_0 && wt != PS_Q8_0) || K < 128 || K % 128 || K > 16384) return false;
+    for (int i = 0; i < a.n_w; i++)
+        if (a.w[i]->dtype != wt || a.w[i]->K != K) return false;
+    const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0), rg = wt == PS_Q4_0 ? 16 : 8, n_tasks = gb_tasks(a);
+    if (epi == 1 && (a.n_w != 2 || a.w[0]->N != a.w[1]->N || a.pro != 1)) return false;
+    if (epi == 2 && (a.n_w != 3 || a.rope_wi0 != 0 || a.pro != 1)) return false;
+    if (n_tasks < 1) return false;
+    const int split_q = n_tasks / (n_tasks < n_cu ? n_tasks : n_cu), tot = (epi == 1 ? 2 : 1) * (int)(K / 128);
+    if (epi != 2 && tot <= 8) return false;
+    if (epi == 0 && a.n_w == 1 && split_q >= 8 && tot <= 64) return false;
+    const size_t smem = (size_t)((K + K / 8 + 15) / 16 * 16) + (size_t)2 * 16 * 3 * 64 * 16 + (size_t)3 * (split_q + 1) * rg * 4;
+    return smem <= 156 * 1024;
+}
+
+int psk_gemvb(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K) {
+    const int wt = a.w[0]->dtype;
+    const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0), rg = wt == PS_Q4_0 ? 16 : 8;
     GBParams p{};
-    int groups_total = 0;
-    for (int i = 0; i < a.n_w; i++) {
-        if (a.w[i]->dtype != wt || a.w[i]->K != K) return -1;
-        const int ng = (int)((a.w[i]->N + rg - 1) / rg);
-        p.w[i] = GBMat{a.w[i]->qs, a.w[i]->aux, a.out[i], a.bias[i], a.w[i]->N, ng};
-        groups_total += ng;
-    }
-    const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0);
-    if (epi == 1 && (a.n_w != 2 || a.w[0]->N != a.w[1]->N || a.pro != 1)) return -1;
-    if (epi == 2) {
-        if (a.n_w != 3 || a.pro != 1) return -1;
-        p.rope = *a.rope;
-    }
-    p.n_w = a.n_w; p.n_units = (int)(K / 128); p.K = (int)K;
-    p.n_tasks = epi == 1 ? p.w[0].n_groups : groups_total;
+    for (int i = 0; i < a.n_w; i++) p.w[i] = GBMat{a.w[i]->qs, a.w[i]->aux, a.out[i], a.bias[i], a.w[i]->N, (int)((a.w[i]->N + rg - 1) / rg)};
+    if (epi == 2) p.rope = *a.rope;
+    p.n_w = a.n_w; p.n_units = (int)(K / 128); p.K = (int)K; p.n_tasks = gb_tasks(a);
     p.residual = a.residual; p.x = a.pro_x; p.nw = a.pro_norm_w; p.eps = a.pro_eps;
     p.aq = act.qs; p.ad = act.d;
     p.act_bytes = (int)((K + K / 8 + 15) / 16 * 16);
-    int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
-    if (grid < 1) return -1;
+    const int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
     p.split_q = p.n_tasks / grid; p.split_r = p.n_tasks % grid;
-    // Measured per launch (profiles/r03_decode_kernel_stats_{1b_q4_0,05b_q8_0}*.txt), this kernel against the register-resident
-    // gemv1 (k_gemv.hip), us: rows of 16+ units 1B QKV 6.8 / 10.7, O 5.7 / 6.2, gate/up 8.7 / 11.7, down 8.0 / 12.3; 0.5B gate/up
-    // (2 x 7 units) 7.5 / 7.8, down (38) 6.5 / 7.9 -- but rows of 7 units (0.5B QKV 5.4 / 4.6, O 5.7 / 5.4: half a chunk per
-    // workgroup, gemv1's 256-thread workgroups start faster) and the long single-matrix stream of the lm_head (1B 40.5 / 37.8,
-    // 0.5B 48 / 41: the one LDS pipe of a workgroup carries three record float4s per unit both ways) go to gemv1.
-    const int tot = epi == 1 ? 2 * p.n_units : p.n_units;
-    if (epi != 2 && tot <= 8) return -1;
-    if (epi == 0 && a.n_w == 1 && p.split_q >= 8 && tot <= 64) return -1;
-    const size_t smem = (size_t)p.act_bytes + (size_t)2 * 16 * 3 * 64 * 16 + (size_t)3 * (p.split_q + 1) * rg * 4;
-    if (smem > 156 * 1024) return -1;
     return wt == PS_Q4_0 ? launch_gb_wt<PS_Q4_0>(st, grid, p, epi, a.pro) : launch_gb_wt<PS_Q8_0>(st, grid, p, epi, a.pro);
 }

@@ -352,22 +352,22 @@ void psk_f16_act(hipStream_t st, int mode, const float *x, const float *norm_w, 
 
 int g_f16_batch = 0; // ps_hip_debug_set(10, v): F16 batches on 0 = the matrix cores where covered (default), 1 = the VALU chains (A/B)
 
+bool psk_gemvh_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
+    if (a.n_w < 1 || a.n_w > 3 || a.rope || (a.silu_pair && a.n_w != 2) || bs < 1 || bs > (1 << 30)) return false;
+    if ((a.pro && !a.pro_x) || (a.pro == 1 && !a.pro_norm_w)) return false;
+    for (int i = 0; i < a.n_w; i++)
+        if (!a.w[i] || a.w[i]->dtype != PS_F16 || a.w[i]->K != K) return false;
+    return !a.silu_pair || (a.w[0]->N == a.w[1]->N && !a.bias[0] && !a.bias[1] && !a.residual);
+}
 int psk_gemvh(hipStream_t st, int n_cu, const psk_gemv_args &a, _Float16 *x16, int64_t K, int64_t bs) {
-    if (a.n_w < 1 || a.n_w > 3 || a.rope || (a.silu_pair && a.n_w != 2) || bs < 1 || bs > (1 << 30)) return 1;
-    if (a.pro != 0 && !a.pro_x) return 1;
-    if (a.pro == 1 && !a.pro_norm_w) return 1;
     HParams p{};
     p.n_w = a.n_w; p.pair = a.silu_pair; p.x = x16; p.K = K; p.bs = (int)bs; p.residual = a.residual;
     int64_t rows = 0;
     for (int i = 0; i < a.n_w; i++) {
-        if (!a.w[i] || a.w[i]->dtype != PS_F16 || a.w[i]->K != K) return 2;
         p.w[i] = (const _Float16 *)a.w[i]->qs; p.N[i] = a.w[i]->N; p.ldo[i] = a.ldo[i]; p.out[i] = a.out[i]; p.bias[i] = a.bias[i];
         rows += a.w[i]->N;
     }
-    if (a.silu_pair) {
-        if (a.w[0]->N != a.w[1]->N || a.bias[0] || a.bias[1] || a.residual) return 3;
-        rows = a.w[0]->N; // one row group takes row r of both matrices
-    }
+    if (a.silu_pair) rows = a.w[0]->N; // one row group takes row r of both matrices
     // one column: the rounding (with its RMSNorm) in the launch's own prologue, into LDS, whenever the column fits (64 KiB)
     int pro = 0;
     if (a.pro && bs == 1 && K * 2 + 16 <= 64 * 1024) {

@@ -414,11 +414,10 @@ void launch_gk(hipStream_t st, int grid, const GKParams &p) {
 template <int WT, int UPW, int DC, int EA, int TPW>
 int launch_gk_ep(hipStream_t st, int grid, const GKParams &p, int epi, int pro) {
     constexpr int NW = 8;
-    if (epi == 2) { if (pro != 1) return -1; launch_gk<WT, NW, UPW, DC, EA, TPW, 2, 1>(st, grid, p); return 0; }
+    if (epi == 2) { launch_gk<WT, NW, UPW, DC, EA, TPW, 2, 1>(st, grid, p); return 0; }
     if constexpr (WT == PS_Q5_K) {
-        if (epi == 1) { if (pro != 1) return -1; launch_gk<WT, NW, UPW, DC, EA, TPW, 1, 1>(st, grid, p); return 0; }
-    } else if (epi != 0) return -1;
-    if (pro == 0) return -1; // (pre-quantized single columns do not occur on the decode path: not instantiated)
+        if (epi == 1) { launch_gk<WT, NW, UPW, DC, EA, TPW, 1, 1>(st, grid, p); return 0; }
+    }
     if (pro == 1) launch_gk<WT, NW, UPW, DC, EA, TPW, 0, 1>(st, grid, p);
     else launch_gk<WT, NW, UPW, DC, EA, TPW, 0, 2>(st, grid, p);
     return 0;
@@ -426,8 +425,7 @@ int launch_gk_ep(hipStream_t st, int grid, const GKParams &p, int epi, int pro) 
 template <int WT, int UPW, int DC, int EA>
 int launch_gk_kc(hipStream_t st, int grid, const GKParams &p, int epi, int pro) {
     if (p.n_units <= 16) return launch_gk_ep<WT, UPW, DC, EA, 2>(st, grid, p, epi, pro);
-    if (p.n_units <= 64) return launch_gk_ep<WT, UPW, DC, EA, 8>(st, grid, p, epi, pro);
-    return -1;
+    return launch_gk_ep<WT, UPW, DC, EA, 8>(st, grid, p, epi, pro); // (n_units <= 64: psk_gemvk_takes)
 }
 template <int WT>
 int launch_gk_wt(hipStream_t st, int grid, const GKParams &p, int epi, int pro) {
@@ -443,40 +441,38 @@ int launch_gk_wt(hipStream_t st, int grid, const GKParams &p, int epi, int pro) 
 
 } // namespace
 
-bool psk_gemvk_covers(int wt, int64_t K) {
+// Single-column Q6_K / Q5_K mat-vec; all matrices of one type.  (Pre-quantized single columns do not occur on the decode path: PRO 0 is not
+// instantiated, those columns take a quantizer launch + k_gemv6.hip.)
+bool psk_gemvk_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
     static const bool off = getenv("PS_NO_GEMVK") != nullptr; // (A/B switch for measurements)
-    return !off && (wt == PS_Q6_K || wt == PS_Q5_K) && K >= 256 && K % 256 == 0 && K <= 16384;
+    if (off || bs != 1 || a.n_w < 1 || a.n_w > 3 || a.pro == 0) return false;
+    const int wt = a.w[0]->dtype;
+    if ((wt != PS_Q6_K && wt != PS_Q5_K) || K < 256 || K % 256 || K > 16384) return false;
+    for (int i = 0; i < a.n_w; i++)
+        if (a.w[i]->dtype != wt || a.w[i]->K != K || a.w[i]->N % 8 || a.w[i]->N < 1) return false;
+    if (a.silu_pair) return wt == PS_Q5_K && a.n_w == 2 && a.w[0]->N == a.w[1]->N && a.pro == 1;
+    if (a.rope) return a.rope_wi0 >= 0 && a.n_w + a.rope_wi0 <= 3 && a.pro == 1 && (wt == PS_Q5_K || a.n_w == 1);
+    return wt == PS_Q5_K || a.n_w == 1;
 }
 
-// Single-column Q6_K / Q5_K mat-vec; all matrices of one type.  Returns -1 when the launch is not covered (the caller falls back
-// to a quantizer launch + k_gemv6.hip).
 int psk_gemvk(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K) {
-    if (a.n_w < 1 || a.n_w > 3) return -1;
     const int wt = a.w[0]->dtype;
-    if (!psk_gemvk_covers(wt, K)) return -1;
     GKParams p{};
     int groups_total = 0;
     for (int i = 0; i < a.n_w; i++) {
         const ps_weight *w = a.w[i];
-        if (w->dtype != wt || w->K != K || w->N % 8) return -1;
         const int ng = (int)(w->N / 8);
         p.w[i] = GKMat{w->qs, w->qh, w->sc, (const uint16_t *)w->aux, a.out[i], a.bias[i], w->N, ng};
         groups_total += ng;
     }
     const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0);
-    if (epi == 1 && (a.n_w != 2 || a.w[0]->N != a.w[1]->N || a.pro != 1)) return -1;
-    if (epi == 2) {
-        if (a.n_w + a.rope_wi0 > 3 || a.rope_wi0 < 0 || a.pro != 1) return -1;
-        p.rope = *a.rope; p.rope_wi0 = a.rope_wi0;
-    }
-    if (wt == PS_Q6_K && (epi == 1 || a.n_w != 1)) return -1;
+    if (epi == 2) { p.rope = *a.rope; p.rope_wi0 = a.rope_wi0; }
     p.n_w = a.n_w; p.n_units = (int)(K / 256); p.K = (int)K;
     p.n_tasks = epi == 1 ? p.w[0].n_groups : groups_total;
     p.residual = a.residual; p.x = a.pro_x; p.nw = a.pro_norm_w; p.eps = a.pro_eps;
     p.aq = act.qs; p.ad = act.d; p.abs16 = act.bs16;
     p.act_bytes = (int)((K + (K / 256) * 4 + (K / 32) * 4 + 15) / 16 * 16);
-    int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
-    if (grid < 1) return -1;
+    const int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
     p.split_q = p.n_tasks / grid; p.split_r = p.n_tasks % grid;
     return wt == PS_Q6_K ? launch_gk_wt<PS_Q6_K>(st, grid, p, epi, a.pro) : launch_gk_wt<PS_Q5_K>(st, grid, p, epi, a.pro);
 }

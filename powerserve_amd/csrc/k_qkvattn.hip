@@ -714,7 +714,7 @@ bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, c
     const psk_rope_kv &rk = *g.rope;
     if (g.out[0] != a.q || rk.rope_table != a.rope_table || rk.rope_pos || rk.k_cache != a.k_cache || rk.v_cache != a.v_cache || rk.head_size != hs ||
         rk.n_dims != a.n_dims || rk.n_ctx != a.n_ctx || rk.kv_dim != a.n_kv_heads * hs || rk.state != a.state || rk.k16 || rk.v16) return false;
-    if (!psk_gemv4_covers(K)) return false; // (PS_NO_GEMV4 switches the mat-vec half off with the mat-vec it restates)
+    if (!psk_gemv4_takes(g, K, 1)) return false; // (its mat-vec half is gemv4's: PS_NO_GEMV4 switches it off too)
     // The launch has head_size / 4 workgroups per kv head: 256 for Llama-3.1-8B's shape, 128 for Llama-3.2-1B's (head size 64) -- half the chip for a mat-vec that the
     // unfused launch spreads over every CU: measured slower there (tools/gpu_fused_stress.py, profiles/r06_fused_stress.txt: 11.9 k vs 12.4 k tok/s on the 2-layer
     // 1B shape in Q4_K, against 4.84 k vs 4.77 k on the 4-layer 8B shape).  Taken only where its grid fills at least three quarters of the chip;

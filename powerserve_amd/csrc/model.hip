@@ -105,124 +105,9 @@ static int dmalloc(ps_hip_model *m, void **p, size_t bytes) {
     return 0;
 }
 
-static int mm(ps_hip_model *m, psk_gemv_args &g, ps_act act, int64_t K, int64_t bs);
-// from this many columns on a launch quantizes its activation ONCE into `act` and goes to the batched kernels (2-4 columns: 4.8-4.9 ms
-// per 8B forward through the batched kernel, 5.4-6.3 ms through the 4-column mat-vec)
-static int gemm_min_bs() {
-    static const int v = getenv("PS_GEMM8_MIN_BS") ? atoi(getenv("PS_GEMM8_MIN_BS")) : 2;
-    return v;
-}
-// Launches whose matrices are not all of one lane-major type (stock Q4_K_M files: attn_v / ffn_down / output in Q6_K next
-// to Q4_K): one launch per matrix, exactly the reference's op sequence (mat-mul, + bias, silu_hadamard).
-static int mm_each(ps_hip_model *m, psk_gemv_args &g, ps_act act, int64_t K, int64_t bs) {
-    ps_hip_ctx *c = m->ctx;
-    float *tmp[2] = {m->g1, m->u1};
-    bool quantized = false; // the K-quants of a group share ONE Q8_K quantization of the activation
-    auto quantize_once = [&]() {
-        if (g.pro && !quantized) psk_quantize_act(c->stream, PS_Q8_K, g.pro == 1 ? 1 : 0, g.pro_x, nullptr, g.pro_norm_w, g.pro_eps, K, bs, act);
-        quantized = true;
-    };
-    bool all5 = g.n_w > 1;
-    for (int i = 0; i < g.n_w; i++) all5 = all5 && g.w[i]->dtype == PS_Q5_K;
-    if (all5 && bs == 1 && !g.rope) { // Q5_K_M: Q / K / V and gate / up as one launch each (when k_gemvk.hip did not take them)
-        quantize_once();
-        psk_gemv6_args a5[3];
-        for (int i = 0; i < g.n_w; i++) a5[i] = psk_gemv6_args{g.w[i], g.silu_pair ? tmp[i] : g.out[i], g.ldo[i], g.bias[i], (i == 0 && !g.silu_pair) ? g.residual : nullptr};
-        if (int rc = psk_gemv5_multi(c->stream, c->n_cu, a5, g.n_w, act, K, bs)) { c->err = "Q5_K mat-vec launch rc=" + std::to_string(rc); return 2; }
-        if (g.silu_pair) psl_silu_hadamard(c->stream, g.out[0], tmp[0], tmp[1], (int64_t)g.ldo[0] * bs);
-        return 0;
-    }
-    for (int i = 0; i < g.n_w; i++) {
-        if (g.w[i]->dtype == PS_F16) { // one matrix of a mixed group: its own launch, the group's epilogue parts as mm_each gives them to every type
-            if (!g.pro || g.rope) { c->err = "F16 mat-mul: needs the fp32 activation and takes no fused RoPE"; return 2; }
-            psk_gemv_args s{};
-            s.n_w = 1; s.w[0] = g.w[i]; s.out[0] = g.silu_pair ? tmp[i] : g.out[i]; s.bias[0] = g.bias[i];
-            s.ldo[0] = g.ldo[i]; s.residual = (i == 0 && !g.silu_pair) ? g.residual : nullptr;
-            s.pro = g.pro; s.pro_x = g.pro_x; s.pro_norm_w = g.pro_norm_w; s.pro_eps = g.pro_eps; // (its own rounding, in its prologue for one column)
-            if (int rc = psk_gemvh(c->stream, c->n_cu, s, m->h16, K, bs)) { c->err = "F16 mat-mul launch rc=" + std::to_string(rc); return 2; }
-            continue;
-        }
-        psk_gemv_args s{};
-        s.n_w = 1; s.w[0] = g.w[i]; s.out[0] = g.silu_pair ? tmp[i] : g.out[i]; s.bias[0] = g.bias[i];
-        s.ldo[0] = g.ldo[i]; s.residual = (i == 0 && !g.silu_pair) ? g.residual : nullptr;
-        s.pro = g.pro; s.pro_x = g.pro_x; s.pro_norm_w = g.pro_norm_w; s.pro_eps = g.pro_eps;
-        s.rope = g.rope; s.rope_wi0 = g.rope_wi0 + i; // (a Q / K / V group split by type: every launch does its part of RoPE + KV append)
-        if (g.w[i]->dtype == PS_Q6_K || g.w[i]->dtype == PS_Q5_K) {
-            if (bs == 1) { // one matrix of a mixed group (Q4_K_M: a Q6_K V next to Q4_K Q and K), or a run of Q5_K ones (Q5_K_M: Q and K next to a Q6_K V): its own prologue
-                int run = 1;
-                while (g.w[i]->dtype == PS_Q5_K && !g.silu_pair && i + run < g.n_w && g.w[i + run]->dtype == PS_Q5_K) run++;
-                for (int j = 1; j < run; j++) { s.w[j] = g.w[i + j]; s.out[j] = g.out[i + j]; s.bias[j] = g.bias[i + j]; s.ldo[j] = g.ldo[i + j]; }
-                s.n_w = run;
-                const int rc = psk_gemvk(c->stream, c->n_cu, s, act, K);
-                if (rc == 0) { i += run - 1; continue; }
-                s.n_w = 1;
-                if (rc != -1 || g.rope) { c->err = "Q5_K / Q6_K mat-vec launch rc=" + std::to_string(rc); return 2; }
-            }
-            quantize_once();
-            psk_gemv6_args a6{g.w[i], s.out[0], s.ldo[0], s.bias[0], s.residual};
-            if (int rc = psk_gemv6(c->stream, c->n_cu, a6, act, K, bs)) { c->err = "Q5_K / Q6_K mat-vec launch rc=" + std::to_string(rc); return 2; }
-        } else {
-            // a run of matrices of one lane-major type goes out as ONE launch (Q4_K_M: Q and K next to a Q6_K V)
-            int run = 1;
-            while (!g.silu_pair && i + run < g.n_w && g.w[i + run]->dtype == g.w[i]->dtype) run++;
-            for (int j = 1; j < run; j++) { s.w[j] = g.w[i + j]; s.out[j] = g.out[i + j]; s.bias[j] = g.bias[i + j]; s.ldo[j] = g.ldo[i + j]; }
-            s.n_w = run;
-            if (mm(m, s, act, K, bs)) return 2;
-            i += run - 1;
-            quantized = bs >= gemm_min_bs() && g.pro != 0 && ps_hip_vec_dot_type(g.w[i]->dtype) == PS_Q8_K; // (exactly when mm() quantized into `act`: a narrower launch quantizes in its own prologue, into LDS)
-        }
-    }
-    if (g.silu_pair) psl_silu_hadamard(c->stream, g.out[0], tmp[0], tmp[1], (int64_t)g.ldo[0] * bs);
-    return 0;
-}
-
-static int mm(ps_hip_model *m, psk_gemv_args &g, ps_act act, int64_t K, int64_t bs) {
-    ps_hip_ctx *c = m->ctx;
-    bool any16 = false, all16 = true;
-    for (int i = 0; i < g.n_w; i++) { any16 = any16 || g.w[i]->dtype == PS_F16; all16 = all16 && g.w[i]->dtype == PS_F16; }
-    if (all16) { // F16 group: ONE launch for all matrices, the activation (with its RMSNorm) rounded to fp16 in its prologue (one column) or once before it
-        if (!g.pro || g.rope) { c->err = "F16 mat-mul: needs the fp32 activation and takes no fused RoPE"; return 2; }
-        if (int rc = psk_gemvh(c->stream, c->n_cu, g, m->h16, K, bs)) { c->err = "F16 mat-mul launch rc=" + std::to_string(rc); return 2; }
-        return 0;
-    }
-    if (any16) return mm_each(m, g, act, K, bs);
-    if (bs == 1 && (g.w[0]->dtype == PS_Q6_K || g.w[0]->dtype == PS_Q5_K)) { // single token: the launch with its fused prologue / epilogue (k_gemvk.hip)
-        const int rc = psk_gemvk(c->stream, c->n_cu, g, act, K); // (-1: mixed types, a pair it does not take, ...)
-        if (rc == 0) return 0;
-        if (rc != -1) { c->err = "Q5_K / Q6_K mat-vec launch rc=" + std::to_string(rc); return 2; }
-    }
-    bool each = g.w[0]->dtype == PS_Q6_K || g.w[0]->dtype == PS_Q5_K;
-    for (int i = 1; i < g.n_w; i++) each = each || g.w[i]->dtype != g.w[0]->dtype;
-    if (each) return mm_each(m, g, act, K, bs);
-    const int vdt = ps_hip_vec_dot_type(g.w[0]->dtype);
-    const int64_t blk = vdt == PS_Q8_0 ? 32 : 256;
-    psk_gemv_args gq = g;
-    int64_t step = 4;
-    if (bs >= gemm_min_bs()) {
-        // batches: the activation is quantized ONCE (with its RMSNorm when the launch carries one) and the weights are
-        // streamed once per column group of up to 16 instead of once per 4 columns
-        if (g.pro) {
-            psk_quantize_act(c->stream, vdt, g.pro == 1 ? 1 : 0, g.pro_x, nullptr, g.pro_norm_w, g.pro_eps, K, bs, act);
-            gq.pro = 0; gq.pro_x = nullptr;
-        }
-        if (!gq.pro) {
-            const int rc = psk_gemm8(c->stream, c->n_cu, gq, act, K, bs);
-            if (rc == 0) return 0;
-            if (rc != -1) { c->err = "gemm launch rc=" + std::to_string(rc); return 2; }
-        }
-        step = psk_gemv_max_cols(g.w[0]->dtype, K);
-    }
-    for (int64_t c0 = 0; c0 < bs; c0 += step) {
-        const int64_t nb = bs - c0 < step ? bs - c0 : step;
-        psk_gemv_args gg = gq;
-        for (int i = 0; i < g.n_w; i++) gg.out[i] = g.out[i] + c0 * g.ldo[i];
-        if (g.residual) gg.residual = g.residual + c0 * g.ldo[0];
-        if (gq.pro) gg.pro_x = g.pro_x + c0 * K;
-        ps_act ac = act;
-        ac.qs += c0 * K; ac.d += c0 * (K / blk); ac.bs16 += c0 * (K / 16);
-        if (int rc = psk_gemv(c->stream, c->n_cu, gg, ac, vdt, K, nb)) { c->err = "gemv launch rc=" + std::to_string(rc); return 2; }
-    }
-    return 0;
+// a quantized / F16 mat-mul of the model (matmul.hip); `act` is carved for this K
+static int mm(ps_hip_model *m, const psk_gemv_args &g, ps_act act, int64_t K, int64_t bs) {
+    return psk_matmul(m->ctx, g, psk_mm_scratch{act, m->h16, {m->g1, m->u1}}, K, bs);
 }
 
 // fp16 prefill perf mode: the first use dequantizes every layer matrix into an fp16 copy (rows through get_rows, the logits buffer as
@@ -280,11 +165,8 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
     hipStream_t st = c->stream;
     const ps_llm_config &f = m->cfg;
     const int64_t dim = f.dim, kvd = f.kv_dim, hid = f.hidden_dim;
-    const int64_t Kmax = dim > hid ? dim : hid;
-    ps_act act = ps_act_carve(m->act_mem, Kmax, m->max_batch);
     // activation rows are laid out with the row strides of the *current* K, so carve per use:
     auto act_for = [&](int64_t K) { return ps_act_carve(m->act_mem, K, m->max_batch); };
-    (void)act;
 
     psl_get_rows(st, m->token_embd, m->tokens_dev, bs, m->x);
     psl_attn_args aa{};
@@ -327,18 +209,12 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
         aa.k_cache = m->k_cache[L]; aa.v_cache = m->v_cache[L];
         const bool kv16 = (m->mode & 8) && !m->k16.empty();
         aa.k16 = kv16 ? m->k16[L] : nullptr; aa.v16 = kv16 ? m->v16[L] : nullptr; aa.part = m->attn_part;
-        // single token, adjacent-pair RoPE: rotation and the KV append ride in the mat-vec epilogue
-        // (mixed types -- Q4_K_M's Q6_K V next to Q4_K Q and K -- and pure Q6_K: one launch per run of a type, each with its part
-        //  of the epilogue, psk_gemv_args::rope_wi0)
-        auto rope_part_ok = [&](const ps_weight *w) {
-            return (w->dtype == PS_Q4_K && psk_gemv4_covers(dim)) || ((w->dtype == PS_Q5_K || w->dtype == PS_Q6_K) && psk_gemvk_covers(w->dtype, dim) && w->N % 8 == 0);
-        };
-        const bool qkv_same = m->wk[L]->dtype == m->wq[L]->dtype && m->wv[L]->dtype == m->wq[L]->dtype;
-        const bool fuse_rope = bs == 1 && !aa.neox && ((qkv_same && psk_gemv_rope_ok(m->wq[L]->dtype, dim)) || (rope_part_ok(m->wq[L]) && rope_part_ok(m->wk[L]) && rope_part_ok(m->wv[L])));
+        // adjacent-pair RoPE: rotation and the KV append ride in the epilogue of the Q / K / V launch(es) wherever the dispatcher's
+        // choice has it -- single tokens (mixed types -- Q4_K_M's Q6_K V next to Q4_K Q and K -- and pure Q6_K: one launch per run of a
+        // type, each with its part of the epilogue, psk_gemv_args::rope_wi0) and Q4_K batches (the chunk mat-mul, k_gemm4k.hip)
         psk_rope_kv rk{m->state, m->rope_table, aa.k_cache, aa.v_cache, (int)f.head_size, (int)f.rope.n_dims, (int)f.seq_len, (int)kvd, aa.rope_pos, aa.k16, aa.v16};
-        // batches of Q4_K weights: the same, in the chunk mat-mul's epilogue (k_gemm4k.hip)
-        const bool fuse_rope_b = bs > 1 && !aa.neox && psk_gemm4k_rope_ok(g, dim, bs);
-        if ((fuse_rope || fuse_rope_b) && !f16) g.rope = &rk;
+        g.rope = &rk;
+        if (f16 || aa.neox || !psk_matmul_fuses_rope(c, g, dim, bs)) g.rope = nullptr;
         bool fused_qa = false;
         if (f16) {
             psf16_rmsnorm_to_h(st, m->x, m->attn_norm[L], f.norm_eps, dim, bs, m->xh);
@@ -357,7 +233,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
         } else if (mm(m, g, a1, dim, bs)) return 2;
 
         aa.kv_stream = kvs_own; aa.dbg = nullptr; // (also when the fused launch declined the shape)
-        if (f16 || (!fuse_rope && !fuse_rope_b)) psl_rope_append(st, aa, bs);
+        if (!g.rope) psl_rope_append(st, aa, bs);
         bool att_quantized = false;
         if (fused_qa) {
         } else if (bs == 1 && !use_tree && kv16 && psl_attn_decode_f16(st, aa)) {
@@ -388,7 +264,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
             aa.qact = ps_act{}; aa.qact_K = dim;
             if (!f16 && bs >= 2 && ps_hip_vec_dot_type(m->wo[L]->dtype) == PS_Q8_K && dim % 256 == 0) {
                 aa.qact = a1;
-                if (!(bs >= ps_gemm4k_min_cols() && dim % 1024 == 0)) { aa.qact.qf = nullptr; aa.qact.mf = nullptr; } // (as psk_quantize_act decides)
+                if (!psk_gemm4k_frag(dim, bs)) { aa.qact.qf = nullptr; aa.qact.mf = nullptr; } // (as psk_quantize_act decides)
                 if (!psl_attn_pv_quantizes(aa, bs)) aa.qact = ps_act{};
             }
             att_quantized = aa.qact.qs != nullptr;
@@ -434,9 +310,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
     }
     if (lm_head) {
         const ps_weight *ow = m->output ? m->output : m->token_embd; // tied lm_head (weights.hpp:67-68)
-        const int vdt = ps_hip_vec_dot_type(ow->dtype);
         ps_act a1 = act_for(dim);
-        (void)vdt;
         psk_gemv_args gl{};
         gl.n_w = 1; gl.w[0] = ow; gl.out[0] = m->logits; gl.ldo[0] = f.vocab_size;
         gl.pro = 1; gl.pro_x = m->x; gl.pro_norm_w = m->output_norm; gl.pro_eps = f.norm_eps;

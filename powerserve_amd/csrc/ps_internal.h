@@ -100,11 +100,14 @@ static inline bool ps_first_on_device(unsigned long long *mask) {
         return 2;                                                                                    \
     } while (0)
 
-// smallest batch the Q4_K chunk mat-mul (k_gemm4k.hip) takes; the quantizer writes the fragment-major copy from here on
+// smallest batch the chunk mat-muls (k_gemm4k.hip) take
 static inline int64_t ps_gemm4k_min_cols() {
     static const int64_t v = [] { const char *e = getenv("PS_GEMM4K_MIN_COLS"); return e ? (int64_t)atoll(e) : (int64_t)2; }();
     return v;
 }
+// the batches whose Q8_K quantization also writes the fragment-major copy (ps_act::qf / mf): every batch that psk_gemm4k_takes,
+// psk_gemm5k_takes or psk_gemm6k_takes can accept
+static inline bool psk_gemm4k_frag(int64_t K, int64_t rows) { return rows >= ps_gemm4k_min_cols() && K % 1024 == 0; }
 static inline size_t ps_act_bytes(int64_t K, int64_t rows) {
     // qs + d (worst case blk 32) + bs16, each 256-B aligned
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -173,43 +176,61 @@ struct psk_gemv_args {
     int rope_wi0;            // with `rope`: which of Q / K / V w[0] is (0 .. 2) when the triple is split over launches by weight type
                              // (Q4_K_M: Q and K in Q4_K, V in Q6_K); n_w + rope_wi0 <= 3.  Taken by gemv4 / gemvk only.
 };
-bool psk_gemv_rope_ok(int wt, int64_t K); // the fused epilogue exists for this weight type / row length
+
+// ---- the quantized / F16 mat-mul (matmul.hip): ONE dispatcher picks the launch(es) of a group of matrices that share an activation,
+// for the model and the op API alike.  The scratch is what the chain may use besides the outputs: `act` (the activation quantized once, at
+// least [bs][K]; ps_act_carve, so that the fragment-major planes exist), `h16` (fp16 columns of the F16 mat-muls, [bs][K]) and `pair`
+// (two fp32 [bs][ldo] buffers: a SiLU pair split over launches).  0, or 2 with c->err set.
+struct psk_mm_scratch {
+    ps_act act;
+    _Float16 *h16;
+    float *pair[2];
+};
+int psk_matmul(ps_hip_ctx *c, const psk_gemv_args &g, const psk_mm_scratch &s, int64_t K, int64_t bs);
+// will psk_matmul(g) do g.rope's RoPE + KV append in the epilogues of its launches (the model plans the rotation before it enqueues)?
+bool psk_matmul_fuses_rope(const ps_hip_ctx *c, const psk_gemv_args &g, int64_t K, int64_t bs);
+
+// Launcher families.  psk_<family>_takes is the whole condition under which psk_<family> runs `a` (its PS_NO_* switch included); the
+// dispatcher asks them in order and calls a launcher only after its predicate said yes.  Launchers return 0 or a launch error.
 size_t psk_gemv_lds_col_bytes(int wt, int64_t K);
-int psk_gemm8(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs); // -1: not covered
+// single-column Q4_K mat-vec with the fused prologues / epilogues (k_gemv4.hip)
+bool psk_gemv4_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
+int psk_gemv4(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K);
+// single-column Q4_0 / Q8_0 mat-vec, producer / chain-wave form (k_gemvb.hip); takes a launch by its share of the chip's n_cu CUs too
+bool psk_gemvb_takes(const psk_gemv_args &a, int64_t K, int64_t bs, int n_cu);
+int psk_gemvb(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K);
+// single-column Q6_K / Q5_K mat-vec with the fused prologues / epilogues (k_gemvk.hip)
+bool psk_gemvk_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
+int psk_gemvk(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K);
+// 1-4 columns of Q4_0 / Q8_0 / Q4_K: gemv1_kernel / gemv_kernel (k_gemv.hip), whatever the others do not take
+bool psk_gemv_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
+int psk_gemv(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs);
+// Q4_K batches on v_mfma_f32_16x16x32_f16, exact integers (k_gemm4k.hip); with a.rope the epilogue rotates and appends
+bool psk_gemm4k_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
 int psk_gemm4k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs);
-bool psk_gemm4k_rope_ok(const psk_gemv_args &a, int64_t K, int64_t bs); // a Q / K / V batch whose RoPE + KV append the mat-mul epilogue will do (set a.rope) // Q4_K batches on v_mfma_f32_16x16x32_f16, exact integers (k_gemm4k.hip); -1: not covered
-int psk_gemv_max_cols(int wt, int64_t K); // widest column group one launch takes (16, 8 or 4; > 4 needs pro == 0)
+// Q4_K / Q4_0 / Q8_0 batches, 8 or 16 pre-quantized columns per workgroup: gemm8m / gemm8b (k_gemv.hip)
+bool psk_gemm8_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
+int psk_gemm8(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs);
+// Q5_K / Q6_K single-matrix batches on the matrix cores (k_gemm4k.hip)
+bool psk_gemm5k_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
+int psk_gemm5k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs);
+bool psk_gemm6k_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
+int psk_gemm6k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs);
+// Q6_K x Q8_K, one matrix, any number of columns; Q5_K x Q8_K, up to three matrices sharing the activation (k_gemv6.hip); act pre-quantized
+bool psk_gemv6_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
+int psk_gemv6(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs);
+bool psk_gemv5_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
+int psk_gemv5(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs);
 static inline int64_t ps_w_rg(int dtype) { return dtype == PS_Q4_0 ? 16 : 8; }
 static inline int64_t ps_w_unit(int dtype) { return dtype == PS_Q4_K ? 256 : 128; }
-// Q6_K / Q5_K x Q8_K (k_gemv6.hip): one matrix, any number of columns (groups of 8 inside); act must be quantized (Q8_K)
-struct psk_gemv6_args {
-    const ps_weight *w;
-    float *out;            // [bs][ldo]
-    int64_t ldo;
-    const float *bias;     // optional [N]
-    const float *residual; // optional, same layout as out (may alias out)
-};
-int psk_gemv6(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int64_t K, int64_t bs);
-int psk_gemv5_multi(hipStream_t st, int n_cu, const psk_gemv6_args *a, int n_w, ps_act act, int64_t K, int64_t bs); // up to 3 Q5_K matrices, one launch
-int psk_gemm5k(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int64_t K, int64_t bs); // Q5_K batches (k_gemm4k.hip); -1: not covered
-int psk_gemm6k(hipStream_t st, int n_cu, const psk_gemv6_args &a, ps_act act, int64_t K, int64_t bs); // Q6_K, >= 17 columns (k_gemm4k.hip); -1: not covered
 // F16 weights (k_gemvh.hip): activation rows -> fp16 rows bit-equal to ggml_fp32_to_fp16_row (mode 1: RMSNorm(x, norm_w, eps) first), and the
 // mat-vec / mat-mul on them (psk_gemv_args without `rope`).  pro 1 / 2: the fp32 column(s) pro_x are rounded (pro 1: after the RMSNorm) in
 // the launch's prologue (one column) or by psk_f16_act into x16 ([bs][K] fp16 scratch) first; pro 0: x16 holds the rounded columns.
-// Batches with K % 8 == 0 run on the matrix cores.  Non-zero: not covered.
+// Batches with K % 8 == 0 run on the matrix cores.
 void psk_f16_act(hipStream_t st, int mode, const float *x, const float *norm_w, float eps, int64_t K, int64_t rows, _Float16 *out);
+bool psk_gemvh_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
 int psk_gemvh(hipStream_t st, int n_cu, const psk_gemv_args &a, _Float16 *x16, int64_t K, int64_t bs);
 int psk_gemv_debug(int key, uint64_t *host_out, int n_words); // timeline buffer: arm / read back
-int psk_gemv(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int vdt, int64_t K, int64_t bs);
-// second-generation single-column Q4_K mat-vec (k_gemv4.hip); -1: not covered, the caller falls back
-int psk_gemv4(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K);
-bool psk_gemv4_covers(int64_t K);
-// single-column Q4_0 / Q8_0 mat-vec, producer / chain-wave form (k_gemvb.hip); -1: not covered, the caller falls back
-int psk_gemvb(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K);
-bool psk_gemvb_covers(int wt, int64_t K);
-// single-column Q6_K / Q5_K mat-vec with the fused prologues / epilogues (k_gemvk.hip); -1: not covered
-int psk_gemvk(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K);
-bool psk_gemvk_covers(int wt, int64_t K);
 unsigned long long *psk_gemv_dbg_buf(int epi, int pro); // timeline slot armed for this (epilogue, prologue) pair, or null
 // the template instance the last quantized mat-vec / mat-mul launch of this process used (rocprofv3's kernel name): bench.py's
 // roofline names the kernel that RAN, not the one it expects
