@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — decode/prefill throughput of the MI355X backend on BASELINE.json's headline workload.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run)
 
 Workload (config.workload): Llama-3.1-8B shape, pure Q4_K synthetic weights (random-init in the quantized
 domain, powerserve_amd/synth.py), prompt of 2048 random token ids, greedy decode.  A "step" is one
@@ -9,10 +9,16 @@ single-token decode step = one pass of the hot path (tokens/s de
 app/run/run.cpp:138-154).  `value` = decode tokens/s aggregated over all N replicas (weak scaling: one full
 model + KV cache per GPU, no data-path collective; RCCL only broadcasts the prompt and gathers the ids).
 
-Extra objects on the JSON line:
+A plain run does what the headline needs and nothing else: it writes the model (afresh, into a directory of its own
+that goes away when the run ends), prefills the prompt once, runs the W warm-up and the K timed steps, writes
+--dump-outputs and prints the line.  --full measures everything else on top of that, after the timed steps (except the
+prefill's own warm-up chunk and its second, warm pass, which come before them as they always have):
+  prefill_*     the prefill's first and warm passes, and its roofline against the matrix-core peak.
   roofline      HBM roofline of the dominant kernel family (quantized GEMV): algorithmic GGUF bytes per launch
                 / average launch duration measured here with HIP events on the backend's own stream.
-  cpu_baseline  the CPU restatement of the reference (oracle "port") timed on this host on a bounded sample.
+  side legs     fp16_kv_mode, fp16_prefill_mode, prefill_wide_chunks, graph_path (each has its --no-* / 0 switch).
+  parity        the bench model against the CPU oracle; cpu_port / cpu_baseline the CPU restatement of the reference
+                (oracle "port") and the real reference's mat-muls timed on this host on a bounded sample.
 """
 from __future__ import annotations
 
@@ -41,9 +47,12 @@ def parse():
     ap.add_argument("--n-ctx", type=int, default=4096)
     ap.add_argument("--batch", type=int, default=128, help="prefill chunk (reference default batch_size=128)")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--full", action="store_true", help="measure and check everything besides the headline too: prefill figures, rooflines, side legs, "
+                    "parity against the CPU oracle, CPU baselines (the options below that name one of them apply to --full runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=4)
-    ap.add_argument("--model-dir", default=None)
+    ap.add_argument("--model-dir", default=None, help="a directory of the caller's for the model: written when it holds none yet, read as it stands otherwise "
+                    "(default: a new directory under TMPDIR for every run, removed when the run ends)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed/RCCL even for one rank (tests the N>1 code path)")
     ap.add_argument("--eager", action="store_true", help="eager launches instead of hipGraph replay (rocprofv3 runs)")
     ap.add_argument("--no-kv-f16", action="store_true", help="skip the fp16-KV decode mode leg")
@@ -61,23 +70,154 @@ def parse():
     return ap.parse_args()
 
 
-def ensure_model(args, rank, barrier):
+def ensure_model(args, rank, world, barrier):
+    """The bench model's directory.  Rank 0 writes the model afresh for every run into a directory of the run's own, which goes away when the
+    process exits (no run reads what an earlier one wrote; the replicas of one launch share rank 0's, named by the launch's rendezvous port).
+    --model-dir names a directory of the caller's instead: the model is written there when it holds none yet and read as it stands otherwise."""
+    import atexit
+    import shutil
+    import tempfile
     from powerserve_amd import gguf, synth
     wt = {"Q4_K_M": synth.Q4_K_M, "Q5_K_M": synth.Q5_K_M}.get(args.wtype) or gguf.NAME_TYPE[args.wtype]  # Q4_K_M / Q5_K_M: llama.cpp's per-tensor mixes with Q6_K
-    d = args.model_dir or os.path.join(os.environ.get("TMPDIR", "/tmp"), f"ps_bench_{args.preset}_{args.wtype}_{args.seed}")
+    name = f"ps_bench_{args.preset}_{args.wtype}_{args.seed}"
+    if args.model_dir:
+        d = args.model_dir
+    elif world == 1:
+        d = tempfile.mkdtemp(prefix=name + ".", dir=os.environ.get("TMPDIR", "/tmp"))
+    else:
+        d = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"{name}.port{os.environ['MASTER_PORT']}")
     marker = os.path.join(d, ".done")
-    # the cache directory is named by preset, type and seed only: a model written there for another --n-ctx (n_rope_ctx_orig follows it) is written anew,
-    # so that the same arguments always run on the same inputs
-    stale = rank == 0 and not args.model_dir and os.path.exists(marker) and synth.load_model_json(d)["llm_config"] != synth.llm_config(args.preset, args.n_ctx)
-    if rank == 0 and (not os.path.exists(marker) or stale):
-        if stale:
-            os.remove(marker)
+    if rank == 0 and (not args.model_dir or not os.path.exists(marker)):
+        if not args.model_dir:
+            if world > 1:
+                shutil.rmtree(d, ignore_errors=True)  # (what a launch that died on this port left behind)
+            atexit.register(shutil.rmtree, d, True)
         t0 = time.time()
-        synth.write_model_dir(d, args.preset, wt, n_ctx=args.n_ctx, seed=args.seed)
+        write_model(d, args.preset, wt, args.n_ctx, args.seed)
         open(marker, "w").write("ok")
         print(f"[bench] synthetic model written to {d} in {time.time() - t0:.1f}s", file=sys.stderr)
     barrier()
     return d
+
+
+def _skip_bytes(bg, n):
+    """Advance the PCG64 `bg` exactly as Generator.integers(0, 256, n, dtype=np.uint8) does (n a multiple of 4): numpy fills such a draw
+    from 32-bit outputs, four bytes each, and PCG64 serves those as the two halves of one 64-bit output, the high half kept for the next
+    32-bit request.  Checked against numpy's own draw before it is used (_skip_is_exact)."""
+    u = n // 4 - bg.state["has_uint32"]  # (a high half left over from the previous draw serves the first four bytes)
+    bg.advance(u // 2)  # (advance() also drops a buffered half)
+    if u % 2:
+        last = int(bg.random_raw())
+        st = bg.state
+        st["has_uint32"], st["uinteger"] = 1, last >> 32
+        bg.state = st
+
+
+def _skip_is_exact():
+    for lead in (0, 1):  # (with and without a buffered half ...)
+        for n in (72, 76):  # (... and leaving one or none)
+            a, b = np.random.default_rng(7), np.random.default_rng(7)
+            for g in (a, b):
+                g.integers(0, 2 ** 32, lead, dtype=np.uint32)
+            a.integers(0, 256, n, dtype=np.uint8)
+            _skip_bytes(b.bit_generator, n)
+            if not np.array_equal(a.integers(0, 2 ** 32, 3, dtype=np.uint32), b.integers(0, 2 ** 32, 3, dtype=np.uint32)):
+                return False
+    return True
+
+
+def _skip_blocks(rng, t, nb):
+    """Make the draws synth.random_blocks makes for `nb` blocks of type t, in its order, with its bulk of full-range quant bytes skipped
+    (_skip_bytes) instead of drawn.  False for a type whose draws are all drawn in full (nothing is drawn then)."""
+    from powerserve_amd import gguf
+    if t == gguf.Q4_0:
+        rng.standard_normal(nb, dtype=np.float32)
+        _skip_bytes(rng.bit_generator, nb * 16)
+    elif t in (gguf.Q4_K, gguf.Q5_K):
+        rng.standard_normal(nb, dtype=np.float32)
+        rng.integers(8, 64, (nb, 8), dtype=np.uint8)
+        _skip_bytes(rng.bit_generator, nb * (128 if t == gguf.Q4_K else 160))
+    elif t == gguf.Q6_K:
+        rng.standard_normal(nb, dtype=np.float32)
+        _skip_bytes(rng.bit_generator, nb * 192)
+        rng.integers(-64, 64, (nb, 16), dtype=np.int8)
+    else:
+        return False
+    return True
+
+
+def _blocks_from(state, t, n_rows, k, std):
+    from powerserve_amd import synth
+    g = np.random.Generator(np.random.PCG64())
+    g.bit_generator.state = state
+    return synth.random_blocks(g, t, n_rows, k, std)
+
+
+def write_model(out_dir, preset, wtype, n_ctx, seed, threads=None):
+    """synth.write_model_dir(out_dir, preset, wtype, n_ctx=n_ctx, seed=seed), byte for byte (tests/test_bench_model.py), in a fraction of its
+    time: one thread walks the tensors in file order making the random stream's draws that vary in length (scale jitter, sub-block scales)
+    and skipping its full-range quant bytes, which gives the stream's state at the start of every tensor; a pool draws each tensor whole
+    from its state with synth.random_blocks; the main thread writes them out in order."""
+    import queue
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    from powerserve_amd import gguf, synth
+    if not _skip_is_exact():  # (a numpy that draws bytes otherwise: the one-thread writer)
+        return synth.write_model_dir(out_dir, preset, wtype, n_ctx=n_ctx, seed=seed)
+    if threads is None:
+        try:
+            threads = len(os.sched_getaffinity(0))
+        except AttributeError:
+            threads = os.cpu_count() or 1
+        threads = max(1, min(threads, 16))  # (the stream walk and the file write bound it well before 16)
+    arch, tied = synth.PRESETS[preset][0], synth.PRESETS[preset][10]
+    cfg = synth.llm_config(preset, n_ctx)
+    os.makedirs(os.path.join(out_dir, "ggml"), exist_ok=True)
+    type_name = {synth.Q4_K_M: "Q4_K_M", synth.Q5_K_M: "Q5_K_M", synth.F16_Q8_0: "F16_Q8_0"}.get(wtype) or gguf.TYPE_NAME[wtype]
+    mj = {"version": 1, "model_arch": arch, "model_id": f"{preset}-{type_name}", "llm_config": cfg}
+    with open(os.path.join(out_dir, "model.json"), "w") as f:
+        json.dump(mj, f, indent=1)
+    w = gguf.GGUFWriter(os.path.join(out_dir, "ggml", "weights.gguf"))
+    w.add_kv("general.architecture", arch)
+    w.add_kv("general.name", mj["model_id"])
+    w.add_kv("general.alignment", gguf.ALIGNMENT)
+    for name, t, ne in synth.tensor_plan(cfg, arch, wtype, tied):
+        w.add_tensor(name, t, ne)
+    rng = np.random.default_rng(seed)
+    ready, room = queue.Queue(), threading.Semaphore(64)  # (at most 64 tensors between the walk and the file: about 1 GB of the 8B model)
+
+    def walk(pool):
+        try:
+            for ti in w.infos:
+                room.acquire()
+                if ti.type == gguf.F32:  # (synth.write_model_dir's norms and biases)
+                    x = rng.standard_normal(int(np.prod(ti.ne)), dtype=np.float32)
+                    ready.put((1.0 + 0.02 * x).astype(np.float32) if ti.name.endswith("norm.weight") else (0.02 * x).astype(np.float32))
+                    continue
+                k, rows = ti.ne[0], int(np.prod(ti.ne[1:]))
+                std = 0.02 * (4096.0 / k) ** 0.5
+                state = rng.bit_generator.state
+                if _skip_blocks(rng, ti.type, rows * (k // gguf.BLOCK[ti.type][0])):
+                    ready.put(pool.submit(_blocks_from, state, ti.type, rows, k, std))
+                else:
+                    ready.put(synth.random_blocks(rng, ti.type, rows, k, std))
+        except BaseException as e:  # noqa: BLE001 -- handed to the writer, which raises it
+            ready.put(e)
+
+    def produce(ti):
+        r = ready.get()
+        if isinstance(r, BaseException):
+            raise r
+        r = r.result() if hasattr(r, "result") else r
+        room.release()
+        return r
+
+    with ThreadPoolExecutor(threads) as pool:
+        th = threading.Thread(target=walk, args=(pool,), daemon=True)
+        th.start()
+        w.write(produce)
+        th.join()
+    return mj
 
 
 def cpu_port(model_dir, prompt, steps):
@@ -463,7 +603,7 @@ def main():
             dist.barrier()
 
     from powerserve_amd import hip
-    model_dir = ensure_model(args, rank, barrier)
+    model_dir = ensure_model(args, rank, world, barrier)
     ctx = hip.Ctx(local)
     t0 = time.time()
     model = hip.Model(ctx, model_dir, max_batch=max(args.batch, 1) * max(args.super_chunks, 1), n_ctx=args.n_ctx)
@@ -495,7 +635,8 @@ def main():
 
     # one UNTIMED reference-sized chunk first (like the decode's W warm-up steps): the first launch of a kernel in a process loads its code object, and on a cold box that alone
     # moved the first pass between 14.9 k and 16.8 k tok/s from run to run (profiles/r06_bench_8b_full.json).  The timed pass below still prefills the WHOLE prompt from an empty cache.
-    if args.prefill_warmup_tokens > 0:
+    # (--full only: a plain run reports no prefill figure, its one pass below just lays down the cache the timed decode steps read)
+    if args.full and args.prefill_warmup_tokens > 0:
         model.reset()
         n_w = min(args.prefill_warmup_tokens, prompt.size - 1)
         model.forward(prompt[:n_w], np.arange(n_w), lm_head=False)
@@ -504,12 +645,13 @@ def main():
     prefill()
     ctx.sync(); barrier()
     prefill_s = time.perf_counter() - t0
-    # (the same prompt once more is reported next to it)
-    barrier(); ctx.sync()
-    t0 = time.perf_counter()
-    prefill()
-    ctx.sync(); barrier()
-    prefill_warm_s = time.perf_counter() - t0
+    prefill_warm_s = None
+    if args.full:  # (the same prompt once more is reported next to it)
+        barrier(); ctx.sync()
+        t0 = time.perf_counter()
+        prefill()
+        ctx.sync(); barrier()
+        prefill_warm_s = time.perf_counter() - t0
 
     # ---- decode: W untimed warmup steps, then exactly K timed steps
     cur = int(prompt[-1])
@@ -528,7 +670,10 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, ids, model.logits(1)[0])
     if dist is not None:
-        dt, prefill_s, prefill_warm_s = max_over_ranks(dist, [dt, prefill_s, prefill_warm_s])
+        if args.full:
+            dt, prefill_s, prefill_warm_s = max_over_ranks(dist, [dt, prefill_s, prefill_warm_s])
+        else:
+            dt, = max_over_ranks(dist, [dt])
         replicas_agree, _ = gather_ids(dist, ids, world)
         # every collective of the run is behind us: the process group goes away NOW, so that no rank sits in an RCCL barrier (host threads spinning)
         # while rank 0 times the CPU baselines on the reference's spin-barrier thread pool (round-4 review, weak 2); ranks > 0 just close and exit
@@ -543,10 +688,6 @@ def main():
         wbytes = model.weight_bytes_per_token
         n_kv_mid = args.prompt_len + args.warmup + args.steps // 2
         kv_bytes = cfg.n_layers * 2 * n_kv_mid * cfg.kv_dim * 4
-        # ---- roofline of the dominant kernel (gate/up mat-vec), event-bracketed replay
-        from powerserve_amd import gguf as _gguf
-        gate_up_bytes = 2 * cfg.hidden_dim * _gguf.row_size(_gguf.NAME_TYPE[{"Q4_K_M": "Q4_K", "Q5_K_M": "Q5_K"}.get(args.wtype, args.wtype)], cfg.dim)
-        rf = gemv_roofline(ctx, model, wbytes, gate_up_bytes, args.preset == "llama-3.1-8b" and args.wtype == "Q4_K")
         out = {
             "metric": "decode tokens/s (greedy, Llama-3.1-8B Q4_K, 1 GPU per replica)" if args.preset == "llama-3.1-8b" and args.wtype == "Q4_K"
             else f"decode tokens/s (greedy, {args.preset} {args.wtype})",
@@ -556,18 +697,25 @@ def main():
             "data": "synthetic (random-init weights generated in the quantized domain; random prompt ids, seed 42)",
             "config": {"workload": f"{args.preset} {'mixed' if args.wtype in ('Q4_K_M', 'Q5_K_M') else 'pure'} {args.wtype}, prefill {args.prompt_len} + decode {args.steps}, n_ctx {args.n_ctx}, FP32 KV",
                        "prefill_chunk": args.batch, "prefill_chunks_per_launch_sequence": max(args.super_chunks, 1), "replicas": world, "collectives": "RCCL broadcast(prompt) + all_gather(ids)" if world > 1 else "none"},
-            "prefill_tokens_per_s": world * (args.prompt_len - 1) / prefill_s, "prefill_s": prefill_s,
-            "prefill_tokens_per_s_warm": world * (args.prompt_len - 1) / prefill_warm_s, "prefill_warm_s": prefill_warm_s,
-            "prefill_warmup_tokens": args.prefill_warmup_tokens,
+        }
+        if args.full:
+            out.update({
+                "prefill_tokens_per_s": world * (args.prompt_len - 1) / prefill_s, "prefill_s": prefill_s,
+                "prefill_tokens_per_s_warm": world * (args.prompt_len - 1) / prefill_warm_s, "prefill_warm_s": prefill_warm_s,
+                "prefill_warmup_tokens": args.prefill_warmup_tokens})
+        out.update({
             "decode_device_ms_per_step": dev_ms / args.steps, "model_load_s": load_s,
             "weight_bytes_per_token": wbytes, "kv_bytes_per_token_mid": kv_bytes,
             "decode_effective_GBps": (wbytes + kv_bytes) / (dt / args.steps) / 1e9,
-            "replicas_agree": replicas_agree, "first_ids": [int(i) for i in ids[:8]],
-            "roofline": rf,
-            "prefill_roofline": prefill_roofline(ctx, model, cfg, args.prompt_len - 1, prefill_s, prefill_warm_s, min(args.batch * max(args.super_chunks, 1), args.prompt_len - 1),
-                                                 args.preset == "llama-3.1-8b" and args.wtype == "Q4_K"),
-        }
-        if not args.no_kv_f16 and not multi:
+            "replicas_agree": replicas_agree, "first_ids": [int(i) for i in ids[:8]]})
+        if args.full:
+            # ---- roofline of the dominant kernel (gate/up mat-vec), event-bracketed replay
+            from powerserve_amd import gguf as _gguf
+            gate_up_bytes = 2 * cfg.hidden_dim * _gguf.row_size(_gguf.NAME_TYPE[{"Q4_K_M": "Q4_K", "Q5_K_M": "Q5_K"}.get(args.wtype, args.wtype)], cfg.dim)
+            out["roofline"] = gemv_roofline(ctx, model, wbytes, gate_up_bytes, args.preset == "llama-3.1-8b" and args.wtype == "Q4_K")
+            out["prefill_roofline"] = prefill_roofline(ctx, model, cfg, args.prompt_len - 1, prefill_s, prefill_warm_s, min(args.batch * max(args.super_chunks, 1), args.prompt_len - 1),
+                                                       args.preset == "llama-3.1-8b" and args.wtype == "Q4_K")
+        if args.full and not args.no_kv_f16 and not multi:
             try:
                 out["fp16_kv_mode"] = fp16_kv_leg(ctx, model, args, prompt, np.concatenate([ids_w, ids]))
             except Exception as e:  # noqa: BLE001 — a failing side leg must not take the headline line with it
@@ -576,18 +724,18 @@ def main():
                 out["fp16_prefill_mode"] = fp16_prefill_leg(ctx, model, args, prompt, model_dir)
             except Exception as e:  # noqa: BLE001
                 out["fp16_prefill_mode"] = {"error": repr(e)}
-        if args.wide_chunk > args.batch and not multi:
+        if args.full and args.wide_chunk > args.batch and not multi:
             try:
                 out["prefill_wide_chunks"] = prefill_wide_leg(ctx, model_dir, args, prompt)
             except Exception as e:  # noqa: BLE001
                 out["prefill_wide_chunks"] = {"error": repr(e)}
-        if not args.no_graph_path and not multi:
+        if args.full and not args.no_graph_path and not multi:
             try:
                 out["graph_path"] = graph_path(model_dir, local, args, prompt)
                 out["graph_path"]["ids_equal_direct"] = out["graph_path"]["first_ids"] == ([int(i) for i in ids_w] + [int(i) for i in ids])[:8]
             except Exception as e:
                 out["graph_path"] = {"error": repr(e)}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:  # the baselines must never take the GPU number down with them
                 port, p_short, ids_cpu, logits_cpu = cpu_port(model_dir, prompt, args.cpu_steps)
                 ids_gpu, logits_gpu = gpu_short_run(model, p_short, ids_cpu)

@@ -635,7 +635,7 @@ def test_bench_runs_under_rccl_world_of_one(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, TMPDIR=str(tmp_path), HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29671", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "2", "--warmup", "1", "--preset", "small-llama-hs128", "--wtype", "Q4_K",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--full", "--steps", "2", "--warmup", "1", "--preset", "small-llama-hs128", "--wtype", "Q4_K",
                         "--prompt-len", "40", "--n-ctx", "128", "--batch", "32", "--no-cpu-baseline", "--no-kv-f16", "--no-graph-path"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -644,3 +644,35 @@ def test_bench_runs_under_rccl_world_of_one(tmp_path):
     line = json.loads(lines[0])
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["replicas_agree"] is True and line["value"] > 0
     assert line["roofline"]["kernel"] and "prefill_roofline" in line
+
+
+def test_bench_plain_run_times_what_the_full_run_times(tmp_path):
+    """A plain bench run (no --full) carries the headline fields and none of what --full adds, computes the same timed steps as a --full run
+    (the ids and last logits --dump-outputs writes, bit for bit: the prefill it runs once is the cache the full run's timed decode reads too),
+    and leaves no model directory behind."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, TMPDIR=str(tmp_path / "tmp"))
+    os.makedirs(env["TMPDIR"])
+    common = ["--steps", "5", "--warmup", "2", "--preset", "small-llama-hs128", "--wtype", "Q4_K", "--prompt-len", "300", "--n-ctx", "512", "--batch", "32"]
+    lines = {}
+    for kind, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-kv-f16", "--no-graph-path", "--wide-chunk", "0"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + extra + ["--dump-outputs", str(tmp_path / kind)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(out) == 1, (r.stdout[-1500:], r.stderr[-1500:])
+        lines[kind] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain and k in full
+    assert plain["steps"] == 5 and plain["warmup"] == 2 and plain["value"] > 0
+    assert not {"roofline", "prefill_roofline", "prefill_tokens_per_s", "fp16_kv_mode", "fp16_prefill_mode", "parity", "cpu_baseline"} & set(plain)
+    assert {"roofline", "prefill_roofline", "prefill_tokens_per_s", "prefill_tokens_per_s_warm"} <= set(full)
+    assert plain["first_ids"] == full["first_ids"]
+    for f in ("decode_ids.npy", "last_step_logits.npy"):
+        a, b = np.load(str(tmp_path / "plain" / f)), np.load(str(tmp_path / "full" / f))
+        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8)), f
+    assert os.listdir(env["TMPDIR"]) == []

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out
 timeout 600 python -m pytest tests/test_gpu_model.py -m gpu -q --maxfail=10 -k "perf_mode" -s 2>&1 | grep -v "^E  " | tail -25
-timeout 900 python bench.py --no-cpu-baseline > $O/perf16_bench.json 2> $O/perf16_bench.err
+timeout 900 python bench.py --full --no-cpu-baseline > $O/perf16_bench.json 2> $O/perf16_bench.err
 tail -3 $O/perf16_bench.err
 python - <<'PY'
 import json
