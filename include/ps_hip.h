@@ -263,6 +263,26 @@ int ps_hip_model_decode_sampled(ps_hip_model *m, int32_t token, int steps, const
 void ps_hip_sample_counters(uint64_t *out2, int reset);
 const char *ps_hip_last_sample_kernels(void);
 
+/* ---- Sequences: several conversations on one model, decoded together (DESIGN.md "Batched decode").
+ * A model holds one or more sequences: a KV cache (K [n_ctx][kv_dim], V [kv_dim][n_ctx] per layer), a position and a visibility table each.  Sequence 0
+ * is the cache ps_hip_model_create allocated; a model on which none of these is called behaves exactly as before.  One sequence is the CURRENT one: every
+ * single-sequence entry point above and below (forward, forward_lowered, prefill, forward_tree, decode_greedy, decode_sampled, kv_*, kv_position, k_cache /
+ * v_cache) works on it -- a prompt gets into sequence s by seq_select(s) + prefill.  Switching drops the captured single-token steps (they hold cache pointers).
+ * seq_reserve: the model holds n_seq sequences afterwards (growing only: fewer than it has is rc 2); rc 1 = out of device memory, the model unchanged.
+ * seq_position: (size_t)-1 for an id out of range. */
+int ps_hip_model_seq_reserve(ps_hip_model *m, int n_seq);
+int ps_hip_model_seq_count(const ps_hip_model *m);
+size_t ps_hip_model_seq_position(const ps_hip_model *m, int seq);
+int ps_hip_model_seq_select(ps_hip_model *m, int seq);
+/* One decode step of n sequences: column i feeds tokens[i] to sequence seq_ids[i] at that sequence's position, appends its K / V there, attends over
+ * that sequence's cache only and advances that sequence by one.  Row i of ps_hip_model_logits is column i's logits (lm_head != 0), argmax_host (optional,
+ * HOST int32[n]) its arg-max.  Column i is bit-identical to ps_hip_model_forward of that token on a one-sequence model with the same history, whoever else
+ * is in the batch.  1 <= n <= min(16, max_batch), ids distinct and < seq_count, every position < n_ctx, no hidden slot (kv_mask) in a participating
+ * sequence, not in the fp16-KV mode (mode bit 3): anything else is rc 2 with nothing advanced. */
+int ps_hip_model_decode_batch(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int lm_head, int32_t *argmax_host);
+/* `steps` such steps, each column fed its own arg-max, without a host round trip per step.  out_ids HOST int32[steps][n]. */
+int ps_hip_model_decode_batch_greedy(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int steps, int32_t *out_ids);
+
 const float *ps_hip_model_logits(const ps_hip_model *m); /* device [max_batch][vocab] */
 /* Arg-max ids of the most recent forward with lm_head (first maximum per token, what greedy_sample / TopK(1) returns: src/sampler/prob_array.cpp:65-67,
  * sampler.cpp:39-56), computed on the device behind the lm_head: 4 bytes per token come to the host instead of vocab x 4 (513 KB for 128 256 logits,

@@ -17,6 +17,12 @@ HIPKV::HIPKV(const ModelConfig::LLMConfig &c, ps_hip_model *model) :
         value_tensors[L].m_data = std::make_shared<HIPBuffer>(stride, (void *)ps_hip_model_v_cache(model, (int)L));
     }
 }
+void HIPKV::rebind() {
+    for (size_t L = 0; L < m_n_layers; L++) {
+        key_tensors[L].get<HIPBuffer>().m_data   = (void *)ps_hip_model_k_cache(m_model, (int)L);
+        value_tensors[L].get<HIPBuffer>().m_data = (void *)ps_hip_model_v_cache(m_model, (int)L);
+    }
+}
 void HIPKV::advance(int n) {
     POWERSERVE_ASSERT(position() + (size_t)n <= m_n_ctx, "the length of kvcache is up to the preset threshold");
     POWERSERVE_ASSERT(ps_hip_model_kv_advance(m_model, (size_t)n) == 0, "kv advance refused: a pending lowered forward has no valid result");

@@ -23,6 +23,7 @@ struct HIPKV {
     ps_hip_model *m_model;
     HIPKV(const ModelConfig::LLMConfig &cfg, ps_hip_model *model);
     size_t position() const { return ps_hip_model_kv_position(m_model); }
+    void rebind(); // the tensors follow the model's current sequence (Model::select_sequence)
     void reset_batch_size(size_t bs) { m_batch_size = bs; }
     void reset_kv_cache() { ps_hip_model_kv_truncate(m_model, kv_size); }
     void advance(int n);

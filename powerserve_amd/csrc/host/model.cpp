@@ -258,6 +258,30 @@ auto Model::decode(const std::vector<Token> &tokens, const std::vector<int> &pos
     return out;
 }
 
+void Model::reserve_sequences(size_t n_seq) {
+    auto &be = backend();
+    if (ps_hip_model_seq_reserve(be.m_model, (int)n_seq)) POWERSERVE_ABORT(std::string("reserve_sequences: ") + ps_hip_last_error(be.m_ctx));
+}
+void Model::select_sequence(size_t seq) {
+    auto &be = backend();
+    if (ps_hip_model_seq_select(be.m_model, (int)seq)) POWERSERVE_ABORT(std::string("select_sequence: ") + ps_hip_last_error(be.m_ctx));
+    be.m_kv->rebind(); // (op-by-op graphs view the cache tensors)
+}
+size_t Model::sequence_count() { return (size_t)ps_hip_model_seq_count(backend().m_model); }
+size_t Model::sequence_position(size_t seq) {
+    POWERSERVE_ASSERT(seq < sequence_count());
+    return ps_hip_model_seq_position(backend().m_model, (int)seq);
+}
+auto Model::decode_batch(const std::vector<int> &seq_ids, const std::vector<Token> &tokens, float *logits_out) -> std::vector<Token> {
+    POWERSERVE_ASSERT(tokens.size() == seq_ids.size() && !tokens.empty());
+    auto &be = backend();
+    std::vector<int32_t> s(seq_ids.begin(), seq_ids.end()), t(tokens.begin(), tokens.end()), ids(tokens.size());
+    if (ps_hip_model_decode_batch(be.m_model, s.data(), t.data(), (int)t.size(), 1, ids.data())) POWERSERVE_ABORT(std::string("decode_batch: ") + ps_hip_last_error(be.m_ctx));
+    if (logits_out && ps_hip_memcpy_d2h(be.m_ctx, logits_out, ps_hip_model_logits(be.m_model), t.size() * (size_t)m_config->llm.vocab_size * 4))
+        POWERSERVE_ABORT(std::string("decode_batch: ") + ps_hip_last_error(be.m_ctx));
+    return std::vector<Token>(ids.begin(), ids.end());
+}
+
 void Model::prefill(const std::vector<Token> &tokens, size_t batch_size) {
     if (tokens.empty()) return;
     POWERSERVE_ASSERT(batch_size > 0);
@@ -407,6 +431,23 @@ int psh_model_decode(void *h, const int32_t *tokens, int n, const int32_t *pos, 
         std::vector<Token> t(tokens, tokens + n);
         std::vector<int> p(pos, pos + n);
         auto r = m->model->decode(t, p, true);
+        for (int i = 0; i < n; i++) ids_out[i] = r[i];
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int psh_model_seq_reserve(void *h, int n_seq) {
+    try { ((psh_model *)h)->model->reserve_sequences((size_t)n_seq); return 0; } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int psh_model_seq_select(void *h, int seq) {
+    try { ((psh_model *)h)->model->select_sequence((size_t)seq); return 0; } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int64_t psh_model_seq_position(void *h, int seq) { // -1: no such sequence
+    try { return (int64_t)((psh_model *)h)->model->sequence_position((size_t)seq); } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+int psh_model_decode_batch(void *h, const int32_t *seq_ids, const int32_t *tokens, int n, int32_t *ids_out, float *logits_out) { // Model::decode_batch
+    try {
+        auto m = (psh_model *)h;
+        auto r = m->model->decode_batch(std::vector<int>(seq_ids, seq_ids + n), std::vector<Token>(tokens, tokens + n), logits_out);
         for (int i = 0; i < n; i++) ids_out[i] = r[i];
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }

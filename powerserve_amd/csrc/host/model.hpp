@@ -81,6 +81,17 @@ struct Model {
     // the same loop with a sampler chain instead of arg-max: logits come back to the host every step (model.hpp:170-183)
     auto generate(const std::vector<Token> &prompt, int steps, size_t batch_size, SamplerChain &sampler) -> std::vector<Token>;
 
+    // ---- sequences: several conversations on one model, decoded together.  The reference's KVCacheInterface has no notion of a sequence (its server keeps a
+    // session map over a one-cache model, app/server/server_handler.hpp), so this extends the facade; it is not a lowering of a reference graph.
+    // The CURRENT sequence is what forward / decode / prefill / generate and the platform's KV position work on.
+    void reserve_sequences(size_t n_seq);
+    void select_sequence(size_t seq);
+    size_t sequence_count();
+    size_t sequence_position(size_t seq);
+    // one greedy step: tokens[i] goes to sequence seq_ids[i] at that sequence's position and advances it; returns the arg-max id per column.
+    // logits_out (optional): host [n][vocab] logits of the columns
+    auto decode_batch(const std::vector<int> &seq_ids, const std::vector<Token> &tokens, float *logits_out = nullptr) -> std::vector<Token>;
+
     hip::HIPBackend &backend() { return *m_platform->hip_backends[m_config->model_id]; }
 
 private:

@@ -1318,7 +1318,215 @@ __global__ __launch_bounds__(64) void argmax_final_kernel(const float *pv, const
     }
 }
 
+// ---------------------------------------------------------------- batched decode: one token per sequence, every sequence on its own cache
+// Column i of the step belongs to sequence tab->col[i].seq and sits at that sequence's position p = col[i].pos: its k / v go to slot p of THAT sequence's
+// caches (s.kv), and it attends over slots [0, p] of them.  Per column the arithmetic is the single-column form of the kernels above -- rope_append_kernel,
+// attn_scores_kernel (32 lanes = the 32 chains of ggml_vec_dot_f32, k-ordered fma, GGML_F32x8_REDUCE) and attn_softmax_pv_kernel (attn_softmax_rows: ggml's
+// max / exp / double sum; V.p along the transposed V row, 32 chains, reduce, n % 32 leftovers) -- with (pos0, bs) = (p, 1), so a column's bits do not depend
+// on who else is in the batch.  Work is divided by score position (32 per workgroup) and by output channel (4 per workgroup), never along a sum, and a
+// workgroup needs no other workgroup: ragged lengths only mean that a short sequence's workgroups past its length leave at once.
+__device__ __forceinline__ psl_attn_args seqs_col_args(const psl_attn_args &a0, const psl_seqs_args &s, const int i) {
+    psl_attn_args a = a0;
+    const ps_seq_col cl = s.tab->col[i];
+    float *const *kv = s.kv + ((int64_t)cl.seq * s.n_layers + s.layer) * 2;
+    a.k_cache = kv[0]; a.v_cache = kv[1];
+    a.n_kv_host = cl.pos + 1; a.bs_host = 1; // att_pos0 = the column's position, att_bs = 1
+    a.tree = nullptr; a.kv_vis = nullptr; a.rope_pos = nullptr;
+    return a;
+}
+
+__global__ void rope_append_seqs_kernel(psl_attn_args a0, psl_seqs_args s, int n) {
+    const int hs = a0.head_size, dim = a0.n_heads * hs, kvd = a0.n_kv_heads * hs, half = a0.n_dims / 2;
+    const int i = blockIdx.y;
+    if (i >= n) return;
+    const psl_attn_args a = seqs_col_args(a0, s, i);
+    const int p = att_pos0(a);
+    const int nq = a.n_heads * (hs / 2), nk = a.n_kv_heads * (hs / 2);
+    for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < nq + nk + kvd; o += gridDim.x * blockDim.x) {
+        if (o < nq + nk) {
+            const bool isq = o < nq;
+            const int oo = isq ? o : o - nq;
+            const int pi = oo % (hs / 2), h = oo / (hs / 2), i0 = 2 * pi;
+            const float *src = isq ? a.q + (int64_t)i * dim + h * hs : a.k + (int64_t)i * kvd + h * hs;
+            float *dst = isq ? a.q + (int64_t)i * dim + h * hs : a.k_cache + (int64_t)p * kvd + h * hs;
+            if (i0 >= a.n_dims) { dst[i0] = src[i0]; dst[i0 + 1] = src[i0 + 1]; continue; }
+            const float c = a.rope_table[(int64_t)p * hs + i0], sn = a.rope_table[(int64_t)p * hs + i0 + 1];
+            const int ia = a.neox ? pi : i0, ib = a.neox ? pi + half : i0 + 1;
+            const float x0 = src[ia], x1 = src[ib];
+            float ra, rb;
+            ps_rope_pair(x0, x1, c, sn, ra, rb);
+            dst[ia] = ra;
+            dst[ib] = rb;
+        } else {
+            const int d = o - nq - nk;
+            a.v_cache[(int64_t)d * a.n_ctx + p] = a.v[(int64_t)i * kvd + d];
+        }
+    }
+}
+
+template <int KVS>
+__device__ __forceinline__ float seqs_ld(const float *p) {
+    if (!KVS) return *p;
+    return __builtin_nontemporal_load(p);
+}
+
+// grid (ceil(n_kv_max / 32), n_kv_heads, n): attn_scores_kernel per column on the column's own K cache
+template <int NV, int KVS>
+__global__ __launch_bounds__(256) void attn_seqs_scores_kernel(psl_attn_args a0, psl_seqs_args s) {
+    const int i = blockIdx.z;
+    const int n_kv = s.tab->col[i].pos + 1;
+    const int j0 = blockIdx.x * 32;
+    if (j0 >= n_kv) return;
+    const psl_attn_args a = seqs_col_args(a0, s, i);
+    const int hs = NV * 32, dim = a.n_heads * hs, kvd = a.n_kv_heads * hs, r2 = a.n_heads / a.n_kv_heads;
+    const int c = threadIdx.x & 31, hw = threadIdx.x >> 5;
+    const int kvh = blockIdx.y;
+    const float *qb = a.q + (int64_t)i * dim + (int64_t)kvh * r2 * hs;
+    float *sb       = a.scores + ((int64_t)i * a.n_heads + (int64_t)kvh * r2) * a.n_ctx;
+    float qf[R2MAX][NV];
+#pragma unroll
+    for (int g = 0; g < R2MAX; g++)
+#pragma unroll
+        for (int m = 0; m < NV; m++) qf[g][m] = (g < r2) ? qb[g * hs + m * 32 + c] : 0.f;
+    float kf[4][NV];
+#pragma unroll
+    for (int rd = 0; rd < 4; rd++) {
+        const int j     = j0 + rd * 8 + hw;
+        const float *kr = a.k_cache + (int64_t)(j < n_kv ? j : 0) * kvd + kvh * hs;
+#pragma unroll
+        for (int m = 0; m < NV; m++) kf[rd][m] = seqs_ld<KVS>(kr + m * 32 + c);
+    }
+#pragma unroll
+    for (int rd = 0; rd < 4; rd++) {
+        const int j     = j0 + rd * 8 + hw;
+        const bool live = j < n_kv;
+#pragma unroll
+        for (int g = 0; g < R2MAX; g++) {
+            if (g < r2) {
+                float sc = 0.f;
+#pragma unroll
+                for (int m = 0; m < NV; m++) sc = __fmaf_rn(kf[rd][m], qf[g][m], sc); // sum = x*y + sum, x = K row (src0)
+                sc = reduce_f32x8x4(sc);
+                if (live && c == 0) sb[(int64_t)g * a.n_ctx + j] = sc;
+            }
+        }
+    }
+}
+
+// grid (head_size / 4, n_kv_heads, n), PV_NT threads: attn_softmax_pv_kernel per column on the column's own V cache
+template <int KVS>
+__global__ __launch_bounds__(PV_NT) void attn_seqs_softmax_pv_kernel(psl_attn_args a0, psl_seqs_args s) {
+    extern __shared__ __attribute__((aligned(16))) float pl[]; // [r2][n_ctx4] e_j, then [4][PV_VSTR] V tile
+    const int i = blockIdx.z, kvh = blockIdx.y;
+    const psl_attn_args a = seqs_col_args(a0, s, i);
+    const int hs = a.head_size, dim = a.n_heads * hs, r2 = a.n_heads / a.n_kv_heads;
+    const int pos0 = att_pos0(a), bs = 1;
+    const int n_kv = pos0 + bs, np = n_kv & ~31, n_kv4 = (n_kv + 3) & ~3;
+    float *vt = pl + (size_t)r2 * (((size_t)a.n_ctx + 3) & ~(size_t)3);
+    __shared__ float redf[R2MAX][PV_NW];
+    __shared__ double redd[R2MAX][PV_NW];
+    __shared__ float invs[R2MAX];
+    const float *vbase = a.v_cache + ((int64_t)kvh * hs + blockIdx.x * 4) * a.n_ctx;
+    float4 ld[PV_LPT];
+    auto load_tile = [&](int t0) { // columns [t0, t0 + PV_TILE) of the 4 channel rows (zero past n_kv)
+#pragma unroll
+        for (int k = 0; k < PV_LPT; k++) {
+            const int f = threadIdx.x + PV_NT * k, row = f / (PV_TILE / 4), col = (f % (PV_TILE / 4)) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row < 4 && t0 + col < n_kv4) v = ad2_ld4<KVS>(vbase + (int64_t)row * a.n_ctx + t0 + col); // n_kv4 <= n_ctx (a multiple of 4): in bounds
+            ld[k] = v;
+        }
+    };
+    auto store_tile = [&]() {
+#pragma unroll
+        for (int k = 0; k < PV_LPT; k++) {
+            const int f = threadIdx.x + PV_NT * k, row = f / (PV_TILE / 4), col = (f % (PV_TILE / 4)) * 4;
+            if (row < 4) *(float4 *)(vt + row * PV_VSTR + col) = ld[k];
+        }
+    };
+    load_tile(0);
+    attn_softmax_rows(a, i, kvh, r2, pos0, bs, n_kv, pl, redf, redd, invs); // (mask: slots below pos0 visible, slot pos0 is the column itself)
+    store_tile();
+    __syncthreads();
+
+    // ---- V·p.  thread: chain c = tid & 31, channel dl = (tid >> 5) & 3, head g = tid >> 7
+    const int c = threadIdx.x & 31, dl = (threadIdx.x >> 5) & 3, g = threadIdx.x >> 7;
+    const bool live = g < r2;
+    const float inv = live ? invs[g] : 0.f;
+    const float *pg = pl + (size_t)(live ? g : 0) * n_kv4;
+    const float *vr = vt + dl * PV_VSTR;
+    float acc = 0.f, out = 0.f;
+    for (int t0 = 0; t0 < n_kv; t0 += PV_TILE) {
+        const int tn = min(PV_TILE, np - t0); // chain columns of this tile (multiple of 32, may be <= 0 on a leftover-only tile)
+        if (t0 > 0) {
+            __syncthreads(); // previous tile consumed
+            store_tile();
+            __syncthreads();
+        }
+        if (t0 + PV_TILE < n_kv) load_tile(t0 + PV_TILE); // next tile streams in while this one is consumed
+        if (live) {
+            int j = c;
+            for (; j + 7 * 32 < tn; j += 8 * 32) {
+                float v[8], e[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) { v[k] = vr[j + 32 * k]; e[k] = pg[t0 + j + 32 * k]; }
+#pragma unroll
+                for (int k = 0; k < 8; k++) acc = __fmaf_rn(v[k], __fmul_rn(e[k], inv), acc); // x = V row (src0), y = p
+            }
+            for (; j < tn; j += 32) acc = __fmaf_rn(vr[j], __fmul_rn(pg[t0 + j], inv), acc);
+            if (t0 + PV_TILE >= n_kv) { // last tile: reduce the 32 chains, then the n%32 leftovers in order
+                float sres = reduce_f32x8x4(acc);
+                for (int jj = np; jj < n_kv; jj++) sres = ps_dot_left(sres, vr[jj - t0], __fmul_rn(pg[jj], inv), jj - np, n_kv - np);
+                out = sres;
+            }
+        }
+    }
+    if (live && c == 0) a.att[(int64_t)i * dim + ((int64_t)kvh * r2 + g) * hs + blockIdx.x * 4 + dl] = out;
+}
+
+__global__ void seqs_advance_kernel(ps_seq_table *tab, const int32_t *argmax, int32_t *tokens, int32_t *ids, int n) {
+    const int i = threadIdx.x;
+    const int k = tab->n_out;
+    __syncthreads();
+    if (i < n) {
+        const int32_t id = argmax[i];
+        tokens[i] = id;
+        ids[(int64_t)k * n + i] = id;
+        tab->col[i].pos++;
+    }
+    if (i == 0) tab->n_out = k + 1;
+}
+
 } // namespace
+
+void psl_rope_append_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs_args &s, int n) {
+    const int per = (a.n_heads + a.n_kv_heads) * (a.head_size / 2) + a.n_kv_heads * a.head_size;
+    hipLaunchKernelGGL(rope_append_seqs_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)n), dim3(256), 0, st, a, s, n);
+}
+
+void psl_attn_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs_args &s, int n) {
+    const int nk = s.n_kv_max > 0 && s.n_kv_max < a.n_ctx ? s.n_kv_max : a.n_ctx;
+    const dim3 gs((unsigned)((nk + 31) / 32), (unsigned)a.n_kv_heads, (unsigned)n);
+#define PS_SEQS_SCORES(NV) do { if (s.kv_stream) hipLaunchKernelGGL((attn_seqs_scores_kernel<NV, 1>), gs, dim3(256), 0, st, a, s); \
+                                else hipLaunchKernelGGL((attn_seqs_scores_kernel<NV, 0>), gs, dim3(256), 0, st, a, s); } while (0)
+    if (a.head_size == 128) PS_SEQS_SCORES(4);
+    else if (a.head_size == 64) PS_SEQS_SCORES(2);
+    else if (a.head_size == 32) PS_SEQS_SCORES(1);
+    else PS_SEQS_SCORES(3); // head_size 96
+#undef PS_SEQS_SCORES
+    static unsigned long long attr = 0; // devices that have the attribute
+    if (ps_first_on_device(&attr)) {
+        (void)hipFuncSetAttribute((const void *)attn_seqs_softmax_pv_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_seqs_softmax_pv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    }
+    const dim3 gp((unsigned)(a.head_size / 4), (unsigned)a.n_kv_heads, (unsigned)n);
+    if (s.kv_stream) hipLaunchKernelGGL(attn_seqs_softmax_pv_kernel<1>, gp, dim3(PV_NT), psl_attn_softmax_pv_lds(a), st, a, s);
+    else hipLaunchKernelGGL(attn_seqs_softmax_pv_kernel<0>, gp, dim3(PV_NT), psl_attn_softmax_pv_lds(a), st, a, s);
+}
+
+void psl_seqs_advance(hipStream_t st, ps_seq_table *tab, const int32_t *argmax, int32_t *tokens, int32_t *ids, int n) {
+    hipLaunchKernelGGL(seqs_advance_kernel, dim3(1), dim3(64), 0, st, tab, argmax, tokens, ids, n);
+}
 
 void psl_rope_append(hipStream_t st, const psl_attn_args &a, int bs) {
     const int64_t n = (int64_t)bs * (a.n_heads + a.n_kv_heads) * (a.head_size / 2) + (int64_t)bs * a.n_kv_heads * a.head_size;

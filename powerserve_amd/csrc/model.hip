@@ -94,6 +94,19 @@ struct ps_hip_model {
     size_t fwd1_hint[2] = {0, 0};
     uint64_t weight_bytes = 0;
     std::vector<void *> owned;
+    // ---- sequences (ps_hip_model_seq_*): k_cache / v_cache / kv_vis_* / n_hidden / position above are the CURRENT sequence's; the others are parked here
+    // (seqs[cur_seq] is stale while that sequence is current).  Sequence 0 is the cache model_create allocated.
+    struct seq_state {
+        std::vector<float *> k_cache, v_cache;
+        uint8_t *kv_vis_dev = nullptr;
+        std::vector<uint8_t> kv_vis_host;
+        size_t n_hidden = 0, position = 0;
+    };
+    std::vector<seq_state> seqs; // empty until the first batched entry point: one sequence, the current one
+    int cur_seq = 0;
+    float **seq_kv_dev = nullptr;      // [n_seq][n_layers][2] cache bases (psl_seqs_args::kv)
+    ps_seq_table *seq_tab = nullptr;   // the batched step's device table
+    int32_t *seq_ids_dev = nullptr;    // [n_ctx][PS_SEQ_COLS_MAX] ids of a greedy batched run
 };
 
 static int mode_env_or();
@@ -160,7 +173,9 @@ static int ensure_perf16(ps_hip_model *m) {
 
 // enqueue one forward over `bs` tokens whose ids are in tokens_dev and whose state is in m->state
 int g_kv_stream_force = getenv("PS_KV_STREAM") ? atoi(getenv("PS_KV_STREAM")) : -1; // ps_hip_debug_set(9, v)
-static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree, bool advance = false, bool use_rope_pos = false, bool sampled = false) {
+// sq: a batched decode step -- column i is a token of ITS OWN sequence (sq->tab); the mat-muls are the column-wise ones of any batch, RoPE + KV append and the
+// attention go per column to that sequence's cache (k_attn.hip, "batched decode")
+static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree, bool advance = false, bool use_rope_pos = false, bool sampled = false, const psl_seqs_args *sq = nullptr) {
     ps_hip_ctx *c = m->ctx;
     hipStream_t st = c->stream;
     const ps_llm_config &f = m->cfg;
@@ -182,7 +197,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
     aa.sync = m->attn_sync;
     // fp16 perf mode (NOT bit-exact, mode bit 5): the layer mat-muls of a prefill batch as dense fp16 GEMMs (perf16.hip); single tokens,
     // tree forwards and anything that produces logits stay on the parity kernels
-    const bool f16 = (m->mode & 32) && bs >= 2 && !lm_head && !use_tree && !use_rope_pos;
+    const bool f16 = (m->mode & 32) && bs >= 2 && !lm_head && !use_tree && !use_rope_pos && !sq;
     if (f16) if (int rc = ensure_perf16(m)) return rc;
     const bool one_launch = (m->mode & 16) == 0; // default; mode bit 4 switches attn_decode2 off (two launches)
     aa.xchg = m->attn_xchg; aa.tick = m->attn_tick; aa.gran = m->attn_gran;
@@ -214,7 +229,9 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
         // type, each with its part of the epilogue, psk_gemv_args::rope_wi0) and Q4_K batches (the chunk mat-mul, k_gemm4k.hip)
         psk_rope_kv rk{m->state, m->rope_table, aa.k_cache, aa.v_cache, (int)f.head_size, (int)f.rope.n_dims, (int)f.seq_len, (int)kvd, aa.rope_pos, aa.k16, aa.v16};
         g.rope = &rk;
-        if (f16 || aa.neox || !psk_matmul_fuses_rope(c, g, dim, bs)) g.rope = nullptr;
+        if (f16 || aa.neox || sq || !psk_matmul_fuses_rope(c, g, dim, bs)) g.rope = nullptr;
+        psl_seqs_args sl{};
+        if (sq) { sl = *sq; sl.layer = (int)L; }
         bool fused_qa = false;
         if (f16) {
             psf16_rmsnorm_to_h(st, m->x, m->attn_norm[L], f.norm_eps, dim, bs, m->xh);
@@ -233,9 +250,12 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
         } else if (mm(m, g, a1, dim, bs)) return 2;
 
         aa.kv_stream = kvs_own; aa.dbg = nullptr; // (also when the fused launch declined the shape)
-        if (!g.rope) psl_rope_append(st, aa, bs);
+        if (sq) psl_rope_append_seqs(st, aa, sl, bs);
+        else if (!g.rope) psl_rope_append(st, aa, bs);
         bool att_quantized = false;
-        if (fused_qa) {
+        if (sq) {
+            psl_attn_seqs(st, aa, sl, bs);
+        } else if (fused_qa) {
         } else if (bs == 1 && !use_tree && kv16 && psl_attn_decode_f16(st, aa)) {
             // fp16-KV decode mode (not bit-exact): split-KV online soft-max over the fp16 mirrors
         } else if (bs == 1 && !use_tree && one_launch && (aa.dbg = psk_gemv_dbg_buf(10, 2), psl_attn_decode2(st, c->n_cu, aa))) { // timeline key 42
@@ -316,7 +336,10 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
         gl.pro = 1; gl.pro_x = m->x; gl.pro_norm_w = m->output_norm; gl.pro_eps = f.norm_eps;
         if (mm(m, gl, a1, dim, bs)) return 2;
         if (sampled) psl_sample(st, m->logits, (int)f.vocab_size, m->sample_dev, m->sample_scratch, nullptr, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
-        else psl_argmax2(st, m->logits, f.vocab_size, bs, m->argmax_dev, m->am_v, m->am_i, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
+        else if (sq) {
+            psl_argmax2(st, m->logits, f.vocab_size, bs, m->argmax_dev, m->am_v, m->am_i, nullptr, nullptr, nullptr);
+            if (advance) psl_seqs_advance(st, m->seq_tab, m->argmax_dev, m->tokens_dev, m->seq_ids_dev, bs);
+        } else psl_argmax2(st, m->logits, f.vocab_size, bs, m->argmax_dev, m->am_v, m->am_i, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
     }
     PS_CHECK(c, hipGetLastError());
     return 0;
@@ -837,6 +860,182 @@ static int decode_sampled_impl(ps_hip_model *m, int32_t token, int steps, const 
     return 0;
 }
 
+// ---- sequences: several KV caches (and positions, and visibility tables) on one model; include/ps_hip.h "Sequences"
+int ps_hip_model_seq_count(const ps_hip_model *m) { return m->seqs.empty() ? 1 : (int)m->seqs.size(); }
+size_t ps_hip_model_seq_position(const ps_hip_model *m, int s) {
+    if (s < 0 || s >= ps_hip_model_seq_count(m)) return (size_t)-1;
+    return s == m->cur_seq ? m->position : m->seqs[s].position;
+}
+static size_t seq_hidden(const ps_hip_model *m, int s) { return s == m->cur_seq ? m->n_hidden : m->seqs[s].n_hidden; }
+// the model holds n_seq sequences and the batched step's tables.  Everything new is allocated before anything of the model changes: a failure (1) leaves it as it was.
+static int seq_grow(ps_hip_model *m, int n_seq) {
+    ps_hip_ctx *c = m->ctx;
+    const int have = ps_hip_model_seq_count(m);
+    if (n_seq < have) n_seq = have;
+    if (!m->seqs.empty() && n_seq == have) return 0;
+    const size_t L = m->cfg.n_layers, nctx = m->cfg.seq_len, cache_bytes = nctx * m->cfg.kv_dim * 4;
+    PS_CHECK(c, hipSetDevice(c->device));
+    PS_CHECK(c, hipStreamSynchronize(c->stream)); // (the table in use is about to be replaced)
+    std::vector<void *> fresh;
+    auto grab = [&](void **p, size_t bytes) {
+        if (ps_dev_malloc(p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); return 1; }
+        fresh.push_back(*p);
+        return 0;
+    };
+    auto fail = [&]() {
+        for (void *p : fresh) (void)ps_dev_free(p);
+        c->err = "seq_reserve: out of device memory for " + std::to_string(n_seq) + " sequences (the model is unchanged)";
+        return 1;
+    };
+    float **kv = nullptr;
+    ps_seq_table *tab = m->seq_tab;
+    int32_t *ids = m->seq_ids_dev;
+    if (grab((void **)&kv, (size_t)n_seq * L * 2 * sizeof(float *))) return fail();
+    if (!tab && (grab((void **)&tab, sizeof(ps_seq_table)) || grab((void **)&ids, nctx * PS_SEQ_COLS_MAX * 4))) return fail();
+    std::vector<ps_hip_model::seq_state> add((size_t)(n_seq - have));
+    for (auto &q : add) {
+        q.k_cache.assign(L, nullptr); q.v_cache.assign(L, nullptr);
+        for (size_t i = 0; i < L; i++)
+            if (grab((void **)&q.k_cache[i], cache_bytes) || grab((void **)&q.v_cache[i], cache_bytes)) return fail();
+        if (grab((void **)&q.kv_vis_dev, nctx)) return fail();
+        q.kv_vis_host.assign(nctx, 1);
+    }
+    for (auto &q : add) {
+        for (size_t i = 0; i < L; i++) { (void)hipMemsetAsync(q.k_cache[i], 0, cache_bytes, c->stream); (void)hipMemsetAsync(q.v_cache[i], 0, cache_bytes, c->stream); }
+        (void)hipMemsetAsync(q.kv_vis_dev, 1, nctx, c->stream);
+    }
+    std::vector<float *> host((size_t)n_seq * L * 2);
+    for (int q = 0; q < n_seq; q++)
+        for (size_t i = 0; i < L; i++) {
+            const bool parked = q < have && q != m->cur_seq;
+            host[((size_t)q * L + i) * 2]     = q >= have ? add[q - have].k_cache[i] : (parked ? m->seqs[q].k_cache[i] : m->k_cache[i]);
+            host[((size_t)q * L + i) * 2 + 1] = q >= have ? add[q - have].v_cache[i] : (parked ? m->seqs[q].v_cache[i] : m->v_cache[i]);
+        }
+    if (hipMemcpyAsync(kv, host.data(), host.size() * sizeof(float *), hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail();
+    }
+    // committed from here on
+    if (m->seq_kv_dev) {
+        auto it = std::find(m->owned.begin(), m->owned.end(), (void *)m->seq_kv_dev);
+        if (it != m->owned.end()) m->owned.erase(it);
+        (void)ps_dev_free(m->seq_kv_dev);
+    }
+    for (void *p : fresh) m->owned.push_back(p);
+    m->seq_kv_dev = kv; m->seq_tab = tab; m->seq_ids_dev = ids;
+    if (m->seqs.empty()) m->seqs.resize(1);
+    for (auto &q : add) m->seqs.push_back(std::move(q));
+    return 0;
+}
+int ps_hip_model_seq_reserve(ps_hip_model *m, int n_seq) {
+    ps_hip_ctx *c = m->ctx;
+    if (int rc = settle_pending(m)) return rc;
+    if (n_seq < 1) PS_FAIL(c, "seq_reserve: at least one sequence");
+    if (n_seq < ps_hip_model_seq_count(m)) PS_FAIL(c, "seq_reserve: the model holds more sequences already (growing only)");
+    if (n_seq > 1 && (m->mode & 8)) PS_FAIL(c, "seq_reserve: the fp16-KV decode mode (mode bit 3) mirrors one cache; it does not combine with sequences");
+    return seq_grow(m, n_seq);
+}
+// The current sequence is what every single-sequence entry point works on.  Captured steps bake the cache and visibility pointers in: a switch drops them
+// (the next decode on the new sequence captures again, as it does after a mode change).
+int ps_hip_model_seq_select(ps_hip_model *m, int s) {
+    ps_hip_ctx *c = m->ctx;
+    if (int rc = settle_pending(m)) return rc;
+    if (s < 0 || s >= ps_hip_model_seq_count(m)) PS_FAIL(c, "seq_select: no such sequence");
+    if (s == m->cur_seq) return 0;
+    auto &old = m->seqs[m->cur_seq];
+    old.k_cache.swap(m->k_cache); old.v_cache.swap(m->v_cache); old.kv_vis_host.swap(m->kv_vis_host);
+    old.kv_vis_dev = m->kv_vis_dev; old.n_hidden = m->n_hidden; old.position = m->position;
+    auto &nw = m->seqs[s];
+    m->k_cache.swap(nw.k_cache); m->v_cache.swap(nw.v_cache); m->kv_vis_host.swap(nw.kv_vis_host);
+    m->kv_vis_dev = nw.kv_vis_dev; m->n_hidden = nw.n_hidden; m->position = nw.position;
+    m->cur_seq = s;
+    m->pin_argmax_n = 0;
+    drop_graphs(m);
+    return 0;
+}
+
+// One batched step (or `steps` greedy ones): argument checks first -- a refusal (2) has changed nothing.
+static int batch_check(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int steps, const char *who) {
+    ps_hip_ctx *c = m->ctx;
+    const std::string w = std::string(who) + ": ";
+    const int cap = m->max_batch < PS_SEQ_COLS_MAX ? m->max_batch : PS_SEQ_COLS_MAX;
+    if (n < 1 || n > cap) PS_FAIL(c, w + "1 <= n <= min(16, max_batch) sequences per step");
+    if (m->mode & 8) PS_FAIL(c, w + "the fp16-KV decode mode (mode bit 3) is not available for batched steps");
+    if (!seq_ids || !tokens) PS_FAIL(c, w + "null argument");
+    for (int i = 0; i < n; i++) {
+        const int s = seq_ids[i];
+        if (s < 0 || s >= ps_hip_model_seq_count(m)) PS_FAIL(c, w + "no such sequence: " + std::to_string(s));
+        for (int j = 0; j < i; j++) if (seq_ids[j] == s) PS_FAIL(c, w + "sequence " + std::to_string(s) + " appears twice in one step");
+        if (seq_hidden(m, s)) PS_FAIL(c, w + "sequence " + std::to_string(s) + " has hidden KV slots (kv_mask); unmask first");
+        if (ps_hip_model_seq_position(m, s) + (size_t)steps > m->cfg.seq_len) PS_FAIL(c, w + "KV cache of sequence " + std::to_string(s) + " is full (n_ctx)");
+        if (tokens[i] < 0 || (uint32_t)tokens[i] >= m->cfg.vocab_size) PS_FAIL(c, w + "token id out of range");
+    }
+    return 0;
+}
+// tables and tokens to the device; the stream is idle afterwards
+static int batch_begin(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, psl_seqs_args *sq) {
+    ps_hip_ctx *c = m->ctx;
+    if (int rc = seq_grow(m, 1)) return rc; // (a model that never reserved: its one sequence, and the tables)
+    PS_CHECK(c, hipSetDevice(c->device));
+    ps_seq_table t{};
+    int64_t rows = 0;
+    int top = 0;
+    for (int i = 0; i < n; i++) {
+        const int pos = (int)ps_hip_model_seq_position(m, seq_ids[i]);
+        t.col[i].seq = seq_ids[i]; t.col[i].pos = pos;
+        rows += pos + 1;
+        if (pos + 1 > top) top = pos + 1;
+    }
+    m->pin_argmax_n = 0;
+    PS_CHECK(c, hipMemcpyAsync(m->seq_tab, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
+    PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    PS_CHECK(c, hipStreamSynchronize(c->stream)); // (both sources are host temporaries)
+    m->pin_busy = false; m->pin_argmax_pending = false;
+    sq->tab = m->seq_tab; sq->kv = m->seq_kv_dev; sq->n_layers = (int)m->cfg.n_layers; sq->layer = 0; sq->n_kv_max = top;
+    // the rows this step reads, K and V of every layer: read once per step, so non-temporal where they cannot stay in the memory-side cache anyway (as enqueue_forward's rule)
+    sq->kv_stream = g_kv_stream_force >= 0 ? g_kv_stream_force : ((int64_t)m->cfg.n_layers * 2 * rows * m->cfg.kv_dim * 4 > ((int64_t)160 << 20) ? 1 : 0);
+    return 0;
+}
+static void batch_advance(ps_hip_model *m, const int32_t *seq_ids, int n, size_t by) {
+    for (int i = 0; i < n; i++) {
+        if (seq_ids[i] == m->cur_seq) m->position += by;
+        else m->seqs[seq_ids[i]].position += by;
+    }
+}
+int ps_hip_model_decode_batch(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int lm_head, int32_t *argmax_host) {
+    ps_hip_ctx *c = m->ctx;
+    if (int rc = settle_pending(m)) return rc;
+    if (int rc = batch_check(m, seq_ids, tokens, n, 1, "decode_batch")) return rc;
+    psl_seqs_args sq{};
+    if (int rc = batch_begin(m, seq_ids, tokens, n, &sq)) return rc;
+    if (int rc = enqueue_forward(m, n, lm_head != 0, false, false, false, false, &sq)) return rc;
+    if (lm_head && argmax_host) PS_CHECK(c, hipMemcpyAsync(argmax_host, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    PS_CHECK(c, hipStreamSynchronize(c->stream));
+    batch_advance(m, seq_ids, n, 1);
+    return 0;
+}
+// `steps` such steps, every column fed its own arg-max.  The table (positions), the next tokens and the ids stay on the device; the host enqueues the steps back to
+// back and waits once.  Eager launches, no hipGraph: the host's enqueue of a step is shorter than the step (DESIGN.md "Batched decode"), and a captured step would
+// have to be keyed by the batch's composition.
+int ps_hip_model_decode_batch_greedy(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int steps, int32_t *out_ids) {
+    ps_hip_ctx *c = m->ctx;
+    if (steps <= 0) return 0;
+    if (int rc = settle_pending(m)) return rc;
+    if (int rc = batch_check(m, seq_ids, tokens, n, steps, "decode_batch_greedy")) return rc;
+    if (!out_ids) PS_FAIL(c, "decode_batch_greedy: null argument");
+    psl_seqs_args sq{};
+    if (int rc = batch_begin(m, seq_ids, tokens, n, &sq)) return rc;
+    const int top0 = sq.n_kv_max;
+    for (int s = 0; s < steps; s++) {
+        sq.n_kv_max = top0 + s;
+        if (int rc = enqueue_forward(m, n, true, false, true, false, false, &sq)) { (void)hipStreamSynchronize(c->stream); return rc; }
+    }
+    PS_CHECK(c, hipMemcpyAsync(out_ids, m->seq_ids_dev, (size_t)steps * n * 4, hipMemcpyDeviceToHost, c->stream));
+    PS_CHECK(c, hipStreamSynchronize(c->stream));
+    batch_advance(m, seq_ids, n, (size_t)steps);
+    return 0;
+}
+
 const float *ps_hip_model_logits(const ps_hip_model *m) { return m->logits; }
 int ps_hip_model_argmax(ps_hip_model *m, int n, int32_t *ids_host) {
     ps_hip_ctx *c = m->ctx;
@@ -956,6 +1155,7 @@ int ps_hip_model_set_mode(ps_hip_model *m, int mode) {
     mode |= mode_env_or();
     if (mode & 64) { m->attn1_disabled = false; mode &= ~64; } // explicit re-arm of the one-launch attention after a time-out
     if (m->attn1_disabled) mode |= 16;                         // sticky: a later set_mode without bit 4 does not bring the form that timed out back
+    if ((mode & 8) && m->seqs.size() > 1) { m->ctx->err = "set_mode: the fp16-KV decode mode mirrors one cache; it does not combine with sequences (seq_reserve)"; return 2; }
     if ((mode & 8) && m->k16.empty()) { // fp16 mirrors of the caches: filled from now on, so the cache must be empty
         if (m->position != 0) { m->ctx->err = "set_mode: the fp16-KV decode mode must be switched on while the cache is empty"; return 2; }
         const size_t n = (size_t)m->cfg.seq_len * m->cfg.kv_dim * 2;

@@ -62,6 +62,29 @@ size_t psl_attn_decode2_xchg_bytes(int n_kv_heads, int n_ctx);
 // layer instead of five; false: not covered, the caller issues the Q / K / V mat-vec (psk_matmul) + psl_attn_decode2
 bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, const psl_attn_args &a);
 size_t psl_attn_softmax_pv_lds(const psl_attn_args &a); // dynamic LDS bytes (grows with n_ctx)
+
+// ---- batched decode: one token per SEQUENCE, each sequence on a KV cache of its own (ps_hip_model_decode_batch)
+// Device table of a batched step.  col[i] = (sequence, position) of batch column i: the token goes to cache slot `pos` of that sequence (its RoPE position too)
+// and attends over slots [0, pos].  A greedy run updates the table itself (psl_seqs_advance): nothing position-dependent comes from the host between steps.
+#define PS_SEQ_COLS_MAX 16 // the narrow mat-mul's width (k_gemm4k.hip)
+struct ps_seq_col { int32_t seq, pos; };
+struct ps_seq_table {
+    int32_t n_out;   // greedy run: steps recorded so far
+    int32_t _pad[3];
+    ps_seq_col col[PS_SEQ_COLS_MAX];
+};
+struct psl_seqs_args {
+    const ps_seq_table *tab;
+    float *const *kv;   // [n_seq][n_layers][2] cache bases: K [n_ctx][kv_dim], V [kv_dim][n_ctx] of (sequence, layer)
+    int n_layers, layer;
+    int n_kv_max;       // upper bound of pos + 1 over the columns, known to the host at enqueue time: sizes the score grid (workgroups past a column's own length exit)
+    int kv_stream;      // as psl_attn_args::kv_stream
+};
+void psl_rope_append_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs_args &s, int n);
+// scores, then soft-max + V.p, of n columns in two launches; no workgroup waits for another (k_attn.hip)
+void psl_attn_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs_args &s, int n);
+// bookkeeping of a greedy batched step: token[i] = argmax[i], ids[n_out * n + i] = argmax[i], col[i].pos++, n_out++
+void psl_seqs_advance(hipStream_t st, ps_seq_table *tab, const int32_t *argmax, int32_t *tokens, int32_t *ids, int n);
 // two-stage arg-max (64 partials per row).  With state != NULL the final stage also does the greedy-decode
 // bookkeeping: token[0] = id, ids[state->n_out++] = id, state->pos0++.
 void psl_argmax2(hipStream_t st, const float *src, int64_t n, int64_t rows, int32_t *out, float *part_v, int *part_i,

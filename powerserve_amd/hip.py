@@ -34,6 +34,7 @@ EXPORTS = [
     "ps_hip_model_v_cache", "ps_hip_model_weight_bytes_per_token", "ps_hip_model_set_mode", "ps_hip_model_bench_gemv", "ps_hip_model_bench_matmul", "ps_hip_debug_timeline", "ps_hip_last_matmul_kernel", "ps_hip_last_attention_kernel", "ps_hip_debug_set", "ps_hip_debug_f16_gemm", "ps_hip_model_forward_tree", "ps_hip_model_prefill", "ps_hip_model_forward_lowered", "ps_hip_model_sync_check", "ps_hip_model_kv_mask",
     "ps_hip_soft_max", "ps_hip_model_kv_copy", "ps_hip_model_kv_save_tokens", "ps_hip_model_kv_unmask_tokens", "ps_hip_model_kv_append_tokens", "ps_hip_model_argmax",
     "ps_hip_sample_covered", "ps_hip_sample", "ps_hip_model_decode_sampled", "ps_hip_sample_counters", "ps_hip_last_sample_kernels",
+    "ps_hip_model_seq_reserve", "ps_hip_model_seq_count", "ps_hip_model_seq_position", "ps_hip_model_seq_select", "ps_hip_model_decode_batch", "ps_hip_model_decode_batch_greedy",
 ]
 SAMPLE_K_MAX, SAMPLE_WINDOW_MAX = 256, 1024  # PS_SAMPLE_K_MAX, PS_SAMPLE_WINDOW_MAX (include/ps_hip.h)
 
@@ -165,7 +166,10 @@ def lib() -> C.CDLL:
         "ps_hip_last_attention_kernel": (C.c_char_p, []),
         "ps_hip_debug_set": (i32, [i32, i32]),
         "ps_hip_sample_covered": (i32, [vp, i32, vp]), "ps_hip_sample": (i32, [vp, vp, i32, vp, vp, vp]),
-        "ps_hip_model_decode_sampled": (i32, [vp, i32, i32, vp, vp, vp]), "ps_hip_sample_counters": (None, [vp, i32]),
+        "ps_hip_model_decode_sampled": (i32, [vp, i32, i32, vp, vp, vp]),
+        "ps_hip_model_seq_reserve": (i32, [vp, i32]), "ps_hip_model_seq_count": (i32, [vp]), "ps_hip_model_seq_position": (sz, [vp, i32]),
+        "ps_hip_model_seq_select": (i32, [vp, i32]), "ps_hip_model_decode_batch": (i32, [vp, vp, vp, i32, i32, vp]),
+        "ps_hip_model_decode_batch_greedy": (i32, [vp, vp, vp, i32, i32, vp]), "ps_hip_sample_counters": (None, [vp, i32]),
         "ps_hip_last_sample_kernels": (C.c_char_p, []),
         "ps_hip_debug_f16_gemm": (i32, [vp, i32, C.c_int64, C.c_int64, i32, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
@@ -461,6 +465,44 @@ class Model:
     def decode_greedy(self, token: int, steps: int) -> np.ndarray:
         out = np.empty(steps, dtype=np.int32)
         self.ctx.check(self.ctx.L.ps_hip_model_decode_greedy(self.h, int(token), steps, _ptr(out)))
+        return out
+
+    # ---- sequences: several KV caches on one model, decoded together (include/ps_hip.h "Sequences")
+    def seq_reserve(self, n_seq: int):
+        self.ctx.check(self.ctx.L.ps_hip_model_seq_reserve(self.h, int(n_seq)))
+
+    @property
+    def seq_count(self) -> int:
+        return self.ctx.L.ps_hip_model_seq_count(self.h)
+
+    def seq_position(self, seq: int) -> int:
+        return self.ctx.L.ps_hip_model_seq_position(self.h, int(seq))
+
+    def seq_select(self, seq: int):
+        """The current sequence: what forward / prefill / decode_greedy / kv_* / position / k_cache / v_cache work on."""
+        self.ctx.check(self.ctx.L.ps_hip_model_seq_select(self.h, int(seq)))
+
+    def decode_batch(self, seq_ids, tokens, lm_head=True, want_logits=True):
+        """One step: tokens[i] goes to sequence seq_ids[i] at its own position.  Returns (logits [n][vocab] | None, argmax [n] | None)."""
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.int32)
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        if seq_ids.size != tokens.size:
+            raise ValueError("decode_batch: one token per sequence")
+        n = tokens.size
+        am = np.empty(n, dtype=np.int32)
+        self.ctx.check(self.ctx.L.ps_hip_model_decode_batch(self.h, _ptr(seq_ids), _ptr(tokens), n, int(lm_head), _ptr(am)))
+        if not lm_head:
+            return None, None
+        return (self.logits(n) if want_logits else None), am
+
+    def decode_batch_greedy(self, seq_ids, tokens, steps: int) -> np.ndarray:
+        """`steps` batched steps, every column fed its own arg-max: ids [steps][n]."""
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.int32)
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        if seq_ids.size != tokens.size:
+            raise ValueError("decode_batch_greedy: one token per sequence")
+        out = np.empty((int(steps), tokens.size), dtype=np.int32)
+        self.ctx.check(self.ctx.L.ps_hip_model_decode_batch_greedy(self.h, _ptr(seq_ids), _ptr(tokens), tokens.size, int(steps), _ptr(out)))
         return out
 
     def decode_sampled(self, token: int, steps: int, cfg: SampleCfg, state: SampleState) -> np.ndarray:

@@ -13,6 +13,7 @@ EXPORTS = ["psh_last_error", "psh_model_load", "psh_model_free", "psh_model_set_
            "psh_model_vocab", "psh_model_forward", "psh_model_generate", "psh_spec_generate", "psh_spec_generate_sampled", "psh_draft_sample", "psh_sampler_create", "psh_sampler_free", "psh_sampler_sample",
            "psh_model_generate_sampled", "psh_token_tree_run", "psh_gguf_summary", "psh_config_summary",
            "psh_model_decode", "psh_model_prefill", "psh_model_plan_cache_hits", "psh_model_set_plan_cache", "psh_graph_softmax", "psh_backend_get_n_tasks", "psh_backend_add_cache", "psh_model_kv_read", "psh_kv_op",
+           "psh_model_seq_reserve", "psh_model_seq_select", "psh_model_seq_position", "psh_model_decode_batch",
            "psh_model_set_device_sampling", "psh_sampler_engine_state", "psh_sampler_device_state", "psh_sampler_is_standard", "psh_sampler_append_noop", "psh_model_generate_with_chain",
            "psh_debug_mt_seed", "psh_debug_mt_next", "psh_debug_discrete", "psh_debug_partial_sort", "psh_debug_chain", "psh_debug_std_mt",
            "psh_debug_std_mt_seed", "psh_debug_std_discrete", "psh_debug_std_partial_sort"]
@@ -52,6 +53,11 @@ def lib() -> C.CDLL:
         L.psh_model_set_plan_cache.argtypes = [C.c_void_p, C.c_int]
         L.psh_model_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.psh_model_prefill.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.psh_model_seq_reserve.argtypes = [C.c_void_p, C.c_int]
+        L.psh_model_seq_select.argtypes = [C.c_void_p, C.c_int]
+        L.psh_model_seq_position.restype = C.c_int64
+        L.psh_model_seq_position.argtypes = [C.c_void_p, C.c_int]
+        L.psh_model_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.psh_graph_softmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.psh_backend_get_n_tasks.argtypes = [C.c_void_p]
         L.psh_backend_add_cache.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
@@ -163,6 +169,33 @@ class HostModel:
         t = np.ascontiguousarray(tokens, dtype=np.int32)
         if self.L.psh_model_prefill(self.h, t.ctypes.data, t.size, int(batch_size)):
             raise HostError(self.L.psh_last_error().decode())
+
+    # ---- sequences (Model::reserve_sequences / select_sequence / decode_batch)
+    def reserve_sequences(self, n_seq: int):
+        if self.L.psh_model_seq_reserve(self.h, int(n_seq)):
+            raise HostError(self.L.psh_last_error().decode())
+
+    def select_sequence(self, seq: int):
+        if self.L.psh_model_seq_select(self.h, int(seq)):
+            raise HostError(self.L.psh_last_error().decode())
+
+    def sequence_position(self, seq: int) -> int:
+        r = self.L.psh_model_seq_position(self.h, int(seq))
+        if r < 0:
+            raise HostError(self.L.psh_last_error().decode())
+        return r
+
+    def decode_batch(self, seq_ids, tokens, want_logits=False):
+        """Model::decode_batch: one greedy step, tokens[i] to sequence seq_ids[i].  Returns ids [n], or (ids, logits [n][vocab])."""
+        s = np.ascontiguousarray(seq_ids, dtype=np.int32)
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        if s.size != t.size or t.size == 0:
+            raise ValueError("decode_batch: one token per sequence, at least one")
+        ids = np.empty(t.size, dtype=np.int32)
+        lg = np.empty((t.size, self.vocab), dtype=np.float32) if want_logits else None
+        if self.L.psh_model_decode_batch(self.h, s.ctypes.data, t.ctypes.data, t.size, ids.ctypes.data, lg.ctypes.data if want_logits else None):
+            raise HostError(self.L.psh_last_error().decode())
+        return (ids, lg) if want_logits else ids
 
     # ---- boundary members no model graph uses (src/graph/graph.cpp:118, ggml.hpp:227,233, core/kv_cache.hpp:120-162)
     def graph_softmax(self, x):
