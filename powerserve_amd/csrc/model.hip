@@ -37,6 +37,13 @@ __global__ void kv_move_kernel(float *k, float *v, _Float16 *k16, _Float16 *v16,
 }
 } // namespace
 
+// a captured single-token step and the KV position it was given as its prefetch hint (n_kv_lo)
+struct step_graph {
+    hipGraphExec_t exec = nullptr;
+    size_t hint = 0;
+};
+enum { G_GREEDY, G_SAMPLED, G_FWD1, G_FWD1_LM, G_COUNT }; // ps_hip_model::graphs: decode_greedy's, decode_sampled's, the lowered forward's without / with lm_head
+
 struct ps_hip_model {
     ps_hip_ctx *ctx = nullptr;
     ps_llm_config cfg{};
@@ -60,12 +67,8 @@ struct ps_hip_model {
     float *attn_xchg = nullptr;    // attn_decode2: scores in flight between workgroups (k_attn.hip)
     unsigned *attn_tick = nullptr; // attn_decode2: [64 * kv head] arrival counters
     unsigned long long *attn_gran = nullptr; // the fused Q / K / V + attention launch: rendezvous A's granules (k_qkvattn.hip)
-    size_t graph_hint = 0;                   // KV position the captured step was given as its prefetch hint (n_kv_lo)
-    int n_kv_hint = 0;             // capture of a single-token forward: the lower bound of n_kv its prefetch hint is baked with
-    int n_kv_host = 0;             // pos0 + bs of the forward being enqueued eagerly (0 while a graph is captured / replayed)
     float *scores = nullptr, *logits = nullptr, *rope_table = nullptr;
     void *act_mem = nullptr;
-    std::vector<float *> k_cache, v_cache;
     std::vector<_Float16 *> k16, v16; // fp16 mirrors, both [n_ctx][kv_dim]: allocated when mode bit 3 is first set
     float *attn_part = nullptr;       // split-KV partials of the fp16 decode attention
     ps_step_state *state = nullptr;
@@ -74,43 +77,67 @@ struct ps_hip_model {
     int *am_i = nullptr;
     uint8_t *tree_dev = nullptr;
     int32_t *rope_pos_dev = nullptr; // [max_batch] RoPE positions of a tree forward
-    uint8_t *kv_vis_dev = nullptr;   // [n_ctx] 1 = visible (KVCacheInterface::mask / unmask)
-    std::vector<uint8_t> kv_vis_host;
-    size_t n_hidden = 0;
-    size_t position = 0;
     int mode = 0;
     psf16 *pf = nullptr;                // fp16 prefill perf mode (mode bit 5): fp16 copies of the layer matrices, fp16 activation scratch
     std::vector<_Float16 *> hq, hk, hv, ho, hg, hu, hd;
     _Float16 *xh = nullptr;
     _Float16 *h16 = nullptr;            // [max_batch][max(dim, hidden)] fp16-rounded activation columns of the F16 mat-muls (k_gemvh.hip); only with F16 weights
     ps_step_state *state_sub = nullptr; // [64] per-chunk states of a super-chunk prefill (ps_hip_model_prefill)
-    int attn_chunk = 0;                 // > 0 while such a forward is enqueued: the attention runs chunk by chunk
-    hipGraphExec_t step_graph = nullptr;
-    hipGraphExec_t sample_graph = nullptr; // ps_hip_model_decode_sampled's captured step (dropped wherever step_graph is)
-    size_t sample_hint = 0;
+    step_graph graphs[G_COUNT];            // the captured single-token steps (dropped together: drop_graphs)
     ps_sample_dev *sample_dev = nullptr;   // sampler configuration + engine state of the current sampled run (allocated at first use)
     void *sample_scratch = nullptr;
-    hipGraphExec_t fwd1_graph[2] = {nullptr, nullptr}; // single-token forward without / with lm_head (the lowered op-API path)
-    size_t fwd1_hint[2] = {0, 0};
     uint64_t weight_bytes = 0;
     std::vector<void *> owned;
-    // ---- sequences (ps_hip_model_seq_*): k_cache / v_cache / kv_vis_* / n_hidden / position above are the CURRENT sequence's; the others are parked here
-    // (seqs[cur_seq] is stale while that sequence is current).  Sequence 0 is the cache model_create allocated.
+    // ---- sequences (ps_hip_model_seq_*): the KV state lives here and nowhere else.  Sequence 0 is the cache model_create allocated; the single-sequence
+    // entry points work on cur().
     struct seq_state {
         std::vector<float *> k_cache, v_cache;
-        uint8_t *kv_vis_dev = nullptr;
+        uint8_t *kv_vis_dev = nullptr;   // [n_ctx] 1 = visible (KVCacheInterface::mask / unmask)
         std::vector<uint8_t> kv_vis_host;
         size_t n_hidden = 0, position = 0;
     };
-    std::vector<seq_state> seqs; // empty until the first batched entry point: one sequence, the current one
+    std::vector<seq_state> seqs; // every sequence, from model_create on
     int cur_seq = 0;
-    float **seq_kv_dev = nullptr;      // [n_seq][n_layers][2] cache bases (psl_seqs_args::kv)
+    seq_state &cur() { return seqs[cur_seq]; }
+    const seq_state &cur() const { return seqs[cur_seq]; }
+    float **seq_kv_dev = nullptr;      // [n_seq][n_layers][2] cache bases (psl_seqs_args::kv); the three device tables are allocated by the first batched entry point
     ps_seq_table *seq_tab = nullptr;   // the batched step's device table
     int32_t *seq_ids_dev = nullptr;    // [n_ctx][PS_SEQ_COLS_MAX] ids of a greedy batched run
 };
 
-static int mode_env_or();
-static void drop_graphs(ps_hip_model *m);
+// PS_HIP_MODE_OR: mode bits OR-ed into every model's mode (A/B runs of unmodified drivers, e.g. bench.py with 16 = two-launch attention)
+static int mode_env_or() {
+    static const int v = [] { const char *e = getenv("PS_HIP_MODE_OR"); return e ? atoi(e) : 0; }();
+    return v;
+}
+static void graph_drop(step_graph &g) {
+    if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+}
+static void drop_graphs(ps_hip_model *m) { // every captured launch plan (they bake the mode, the prefetch hint and the visibility pointers in)
+    for (auto &g : m->graphs) graph_drop(g);
+}
+// the captured step carries the position it was captured at as a prefetch hint (n_kv_lo): keep it a LOWER bound that
+// is not far behind (a stale hint costs time, never results)
+static void graph_drop_if_stale(step_graph &g, size_t pos) {
+    if (pos < g.hint || pos >= g.hint + 1024) graph_drop(g);
+}
+// capture what `enqueue` puts on the stream into g (nothing executes), with `pos` as its hint.  False: g is empty, and c->err says why
+template <class F> static bool graph_capture(ps_hip_model *m, step_graph &g, size_t pos, F &&enqueue) {
+    ps_hip_ctx *c = m->ctx;
+    hipGraph_t gr = nullptr;
+    int rc = 0;
+    hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        rc = enqueue();
+        e = hipStreamEndCapture(c->stream, &gr);
+    }
+    if (!rc && e == hipSuccess) e = hipGraphInstantiate(&g.exec, gr, nullptr, nullptr, 0);
+    if (gr) (void)hipGraphDestroy(gr);
+    if (!rc && e != hipSuccess) c->err = hipGetErrorString(e);
+    if (rc || e != hipSuccess) { g.exec = nullptr; return false; }
+    g.hint = pos;
+    return true;
+}
 static int dmalloc(ps_hip_model *m, void **p, size_t bytes) {
     ps_hip_ctx *c = m->ctx;
     PS_CHECK(c, ps_dev_malloc(p, bytes ? bytes : 16));
@@ -171,14 +198,66 @@ static int ensure_perf16(ps_hip_model *m) {
     return 0;
 }
 
-// enqueue one forward over `bs` tokens whose ids are in tokens_dev and whose state is in m->state
+// The mat-mul argument groups of a forward, built HERE and nowhere else: a layer's [Wq|Wk|Wv] (bias, RMSNorm prologue), Wo, the [Wgate|Wup] SiLU pair, Wdown,
+// and the lm_head (L unused).  What a caller decides per launch (the RoPE epilogue, whether `down` quantizes in its prologue) it sets on the result.
+enum mm_group { MM_QKV, MM_O, MM_GATE_UP, MM_DOWN, MM_LM_HEAD };
+static psk_gemv_args mm_args(const ps_hip_model *m, mm_group which, uint32_t L) {
+    const ps_llm_config &f = m->cfg;
+    const int64_t dim = f.dim, kvd = f.kv_dim, hid = f.hidden_dim;
+    psk_gemv_args g{};
+    switch (which) {
+    case MM_QKV:
+        g.n_w = 3;
+        g.w[0] = m->wq[L]; g.w[1] = m->wk[L]; g.w[2] = m->wv[L];
+        g.out[0] = m->q; g.out[1] = m->k; g.out[2] = m->v;
+        g.ldo[0] = dim; g.ldo[1] = kvd; g.ldo[2] = kvd;
+        if (m->qwen2) { g.bias[0] = m->bq[L]; g.bias[1] = m->bk[L]; g.bias[2] = m->bv[L]; }
+        g.pro = 1; g.pro_x = m->x; g.pro_norm_w = m->attn_norm[L]; g.pro_eps = f.norm_eps; // RMSNorm + quantize in the prologue
+        break;
+    case MM_O:
+        g.n_w = 1; g.w[0] = m->wo[L]; g.out[0] = m->x; g.ldo[0] = dim; g.residual = m->x;
+        g.pro = 2; g.pro_x = m->att;
+        break;
+    case MM_GATE_UP:
+        g.n_w = 2; g.w[0] = m->wg[L]; g.w[1] = m->wu[L]; g.out[0] = m->hb; g.out[1] = m->hb; g.ldo[0] = hid; g.ldo[1] = hid;
+        g.silu_pair = 1;
+        g.pro = 1; g.pro_x = m->x; g.pro_norm_w = m->ffn_norm[L]; g.pro_eps = f.norm_eps;
+        break;
+    case MM_DOWN: // (pro 0: the activation is quantized by the caller, or it selects the prologue)
+        g.n_w = 1; g.w[0] = m->wd[L]; g.out[0] = m->x; g.ldo[0] = dim; g.residual = m->x;
+        break;
+    case MM_LM_HEAD:
+        g.n_w = 1; g.w[0] = m->output ? m->output : m->token_embd; // tied lm_head (weights.hpp:67-68)
+        g.out[0] = m->logits; g.ldo[0] = f.vocab_size;
+        g.pro = 1; g.pro_x = m->x; g.pro_norm_w = m->output_norm; g.pro_eps = f.norm_eps;
+        break;
+    }
+    return g;
+}
+
 int g_kv_stream_force = getenv("PS_KV_STREAM") ? atoi(getenv("PS_KV_STREAM")) : -1; // ps_hip_debug_set(9, v)
-// sq: a batched decode step -- column i is a token of ITS OWN sequence (sq->tab); the mat-muls are the column-wise ones of any batch, RoPE + KV append and the
-// attention go per column to that sequence's cache (k_attn.hip, "batched decode")
-static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree, bool advance = false, bool use_rope_pos = false, bool sampled = false, const psl_seqs_args *sq = nullptr) {
+// What one forward consists of: everything enqueue_forward is told, by name (nothing is set on the model before a call and cleared after it)
+struct fwd_opts {
+    bool lm_head = false;  // final norm + lm_head + arg-max (or the sampler chain)
+    bool tree = false;     // tree_dev is the attention's mask
+    bool rope_pos = false; // RoPE positions from rope_pos_dev (a tree forward)
+    bool advance = false;  // with lm_head: the step feeds its own id back and moves the device-side state on (the decode loops)
+    bool sampled = false;  // with lm_head: the sampler chain (sample_dev) in place of the arg-max
+    // sq: a batched decode step -- column i is a token of ITS OWN sequence (sq->tab); the mat-muls are the column-wise ones of any batch, RoPE + KV append and the
+    // attention go per column to that sequence's cache (k_attn.hip, "batched decode")
+    const psl_seqs_args *sq = nullptr;
+    int n_kv_host = 0;     // pos0 + bs of a forward that is enqueued eagerly (0 while a graph is captured / replayed)
+    int n_kv_hint = 0;     // capture of a single-token forward: the lower bound of n_kv its prefetch hint is baked with
+    int attn_chunk = 0;    // > 0: a super-chunk (ps_hip_model_prefill), the attention runs chunk by chunk
+};
+// enqueue one forward over `bs` tokens whose ids are in tokens_dev and whose state is in m->state
+static int enqueue_forward(ps_hip_model *m, int bs, const fwd_opts &o) {
     ps_hip_ctx *c = m->ctx;
     hipStream_t st = c->stream;
     const ps_llm_config &f = m->cfg;
+    const ps_hip_model::seq_state &kv = m->cur();
+    const bool lm_head = o.lm_head, use_tree = o.tree, use_rope_pos = o.rope_pos;
+    const psl_seqs_args *sq = o.sq;
     const int64_t dim = f.dim, kvd = f.kv_dim, hid = f.hidden_dim;
     // activation rows are laid out with the row strides of the *current* K, so carve per use:
     auto act_for = [&](int64_t K) { return ps_act_carve(m->act_mem, K, m->max_batch); };
@@ -190,10 +269,10 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
     aa.q = m->q; aa.k = m->k; aa.v = m->v; aa.scores = m->scores; aa.att = m->att;
     aa.tree = use_tree ? m->tree_dev : nullptr;
     aa.rope_pos = use_rope_pos ? m->rope_pos_dev : nullptr;
-    aa.kv_vis = m->n_hidden ? m->kv_vis_dev : nullptr;
+    aa.kv_vis = kv.n_hidden ? kv.kv_vis_dev : nullptr;
     aa.scale = 1.0f / sqrtf((float)f.head_size);
-    aa.n_kv_host = m->n_kv_host;
-    aa.bs_host = m->n_kv_host > 0 ? bs : 0;
+    aa.n_kv_host = o.n_kv_host;
+    aa.bs_host = o.n_kv_host > 0 ? bs : 0;
     aa.sync = m->attn_sync;
     // fp16 perf mode (NOT bit-exact, mode bit 5): the layer mat-muls of a prefill batch as dense fp16 GEMMs (perf16.hip); single tokens,
     // tree forwards and anything that produces logits stay on the parity kernels
@@ -206,22 +285,16 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
     // 1024, +2.2 % behind 2048); the attention launch of its own (attn_decode2) gains where the whole cache -- every layer, K and V -- is more than the memory-side cache keeps
     // from token to token (8B behind 2048 tokens, 537 MB: +0.8 %) and loses where it fits (Llama-3.2-1B behind 512 tokens, 42 MB: -2.2 %).  PS_KV_STREAM=0 / 1 forces both (A/B).
     const int kvs_force = g_kv_stream_force; // (PS_KV_STREAM / ps_hip_debug_set(9, v): -1 by the rule below, 0 / 1 forced)
-    const int64_t n_kv_now = m->n_kv_host > 0 ? m->n_kv_host : (m->n_kv_hint > 0 ? m->n_kv_hint : (int64_t)m->position);
+    const int n_kv_now = o.n_kv_host > 0 ? o.n_kv_host : (o.n_kv_hint > 0 ? o.n_kv_hint : (int)kv.position);
     const int kvs_fused = kvs_force >= 0 ? kvs_force : 1;
     const int kvs_own = kvs_force >= 0 ? kvs_force : ((int64_t)f.n_layers * 2 * n_kv_now * kvd * 4 > ((int64_t)160 << 20) ? 1 : 0);
     aa.kv_stream = kvs_own;
-    aa.n_kv_lo = m->n_kv_host > 0 ? m->n_kv_host : (m->n_kv_hint > 0 ? m->n_kv_hint : (int)m->position); // (a hint: rows below it are requested before the device-side position has arrived)
+    aa.n_kv_lo = n_kv_now; // (a hint: rows below it are requested before the device-side position has arrived)
 
     for (uint32_t L = 0; L < f.n_layers; L++) {
         ps_act a1 = act_for(dim);
-        psk_gemv_args g{};
-        g.n_w = 3;
-        g.w[0] = m->wq[L]; g.w[1] = m->wk[L]; g.w[2] = m->wv[L];
-        g.out[0] = m->q; g.out[1] = m->k; g.out[2] = m->v;
-        g.ldo[0] = dim; g.ldo[1] = kvd; g.ldo[2] = kvd;
-        if (m->qwen2) { g.bias[0] = m->bq[L]; g.bias[1] = m->bk[L]; g.bias[2] = m->bv[L]; }
-        g.pro = 1; g.pro_x = m->x; g.pro_norm_w = m->attn_norm[L]; g.pro_eps = f.norm_eps; // RMSNorm + quantize in the prologue
-        aa.k_cache = m->k_cache[L]; aa.v_cache = m->v_cache[L];
+        psk_gemv_args g = mm_args(m, MM_QKV, L);
+        aa.k_cache = kv.k_cache[L]; aa.v_cache = kv.v_cache[L];
         const bool kv16 = (m->mode & 8) && !m->k16.empty();
         aa.k16 = kv16 ? m->k16[L] : nullptr; aa.v16 = kv16 ? m->v16[L] : nullptr; aa.part = m->attn_part;
         // adjacent-pair RoPE: rotation and the KV append ride in the epilogue of the Q / K / V launch(es) wherever the dispatcher's
@@ -260,16 +333,16 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
             // fp16-KV decode mode (not bit-exact): split-KV online soft-max over the fp16 mirrors
         } else if (bs == 1 && !use_tree && one_launch && (aa.dbg = psk_gemv_dbg_buf(10, 2), psl_attn_decode2(st, c->n_cu, aa))) { // timeline key 42
             aa.dbg = nullptr;
-        } else if (m->attn_chunk > 0 && bs > m->attn_chunk) {
+        } else if (o.attn_chunk > 0 && bs > o.attn_chunk) {
             // a super-chunk of several reference-sized chunks (ps_hip_model_prefill): the mat-muls above and below take all bs columns
             // at once (they are column-wise: chunking cannot change their bits), the attention runs chunk by chunk with the n_kv the
             // reference's chunk would have seen -- its soft-max and V.p sums depend on where a chunk ends
-            for (int c0 = 0, k = 0; c0 < bs; c0 += m->attn_chunk, k++) {
-                const int nb = bs - c0 < m->attn_chunk ? bs - c0 : m->attn_chunk;
+            for (int c0 = 0, k = 0; c0 < bs; c0 += o.attn_chunk, k++) {
+                const int nb = bs - c0 < o.attn_chunk ? bs - c0 : o.attn_chunk;
                 psl_attn_args as = aa;
                 as.state = m->state_sub + k;
                 as.q = m->q + (int64_t)c0 * dim; as.att = m->att + (int64_t)c0 * dim;
-                as.n_kv_host = m->n_kv_host > 0 ? m->n_kv_host - (bs - c0 - nb) : 0;
+                as.n_kv_host = o.n_kv_host > 0 ? o.n_kv_host - (bs - c0 - nb) : 0;
                 as.bs_host = as.n_kv_host > 0 ? nb : 0;
                 as.qact = ps_act{}; as.dbg = nullptr;
                 psl_attn_scores(st, as, nb);
@@ -293,18 +366,12 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
             aa.dbg = nullptr;
         }
 
-        psk_gemv_args go{};
-        go.n_w = 1; go.w[0] = m->wo[L]; go.out[0] = m->x; go.ldo[0] = dim; go.residual = m->x;
-        go.pro = 2; go.pro_x = m->att;
+        psk_gemv_args go = mm_args(m, MM_O, L);
         if (att_quantized) { go.pro = 0; go.pro_x = nullptr; } // (the V.p kernel left `att` quantized in a1)
         ps_act a2 = act_for(hid);
         const int vdt_d = ps_hip_vec_dot_type(m->wd[L]->dtype);
-        psk_gemv_args gf{};
-        gf.n_w = 2; gf.w[0] = m->wg[L]; gf.w[1] = m->wu[L]; gf.out[0] = m->hb; gf.out[1] = m->hb; gf.ldo[0] = hid; gf.ldo[1] = hid;
-        gf.silu_pair = 1;
-        gf.pro = 1; gf.pro_x = m->x; gf.pro_norm_w = m->ffn_norm[L]; gf.pro_eps = f.norm_eps;
-        psk_gemv_args gd{};
-        gd.n_w = 1; gd.w[0] = m->wd[L]; gd.out[0] = m->x; gd.ldo[0] = dim; gd.residual = m->x;
+        const psk_gemv_args gf = mm_args(m, MM_GATE_UP, L);
+        psk_gemv_args gd = mm_args(m, MM_DOWN, L);
         if (f16) { // x += O att;  x += down(silu(gate x') * up x'),  x' = rmsnorm(x): residuals through beta = 1
             psf16_to_h(st, m->att, (int64_t)bs * dim, m->xh);
             if (psf16_gemm(c, m->pf, m->ho[L], dim, dim, m->xh, bs, m->x, dim, 1.f)) return 2;
@@ -329,13 +396,9 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
         if (mm(m, gd, a2, hid, bs)) return 2;
     }
     if (lm_head) {
-        const ps_weight *ow = m->output ? m->output : m->token_embd; // tied lm_head (weights.hpp:67-68)
-        ps_act a1 = act_for(dim);
-        psk_gemv_args gl{};
-        gl.n_w = 1; gl.w[0] = ow; gl.out[0] = m->logits; gl.ldo[0] = f.vocab_size;
-        gl.pro = 1; gl.pro_x = m->x; gl.pro_norm_w = m->output_norm; gl.pro_eps = f.norm_eps;
-        if (mm(m, gl, a1, dim, bs)) return 2;
-        if (sampled) psl_sample(st, m->logits, (int)f.vocab_size, m->sample_dev, m->sample_scratch, nullptr, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
+        if (mm(m, mm_args(m, MM_LM_HEAD, 0), act_for(dim), dim, bs)) return 2;
+        const bool advance = o.advance;
+        if (o.sampled) psl_sample(st, m->logits, (int)f.vocab_size, m->sample_dev, m->sample_scratch, nullptr, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
         else if (sq) {
             psl_argmax2(st, m->logits, f.vocab_size, bs, m->argmax_dev, m->am_v, m->am_i, nullptr, nullptr, nullptr);
             if (advance) psl_seqs_advance(st, m->seq_tab, m->argmax_dev, m->tokens_dev, m->seq_ids_dev, bs);
@@ -343,6 +406,75 @@ static int enqueue_forward(ps_hip_model *m, int bs, bool lm_head, bool use_tree,
     }
     PS_CHECK(c, hipGetLastError());
     return 0;
+}
+
+// Wait for the stream.  It is idle afterwards: everything enqueued before this point has run, so no upload from the pinned token word is queued any
+// more and the arg-max ids copied behind a lowered forward have arrived.
+static hipError_t sync_stream(ps_hip_model *m) {
+    const hipError_t e = hipStreamSynchronize(m->ctx->stream);
+    if (e == hipSuccess) { m->pin_busy = false; m->pin_argmax_pending = false; }
+    return e;
+}
+static int check_tokens(ps_hip_model *m, const int32_t *tokens, int n, const char *who) {
+    for (int i = 0; i < n; i++)
+        if (tokens[i] < 0 || (uint32_t)tokens[i] >= m->cfg.vocab_size) PS_FAIL(m->ctx, std::string(who) + ": token id out of range");
+    return 0;
+}
+// KVCache::advance_tokens unmasks the slots it walks over (core/kv_cache.hpp:249-255)
+static void unmask_range(ps_hip_model *m, size_t from, size_t n) {
+    ps_hip_model::seq_state &kv = m->cur();
+    if (!kv.n_hidden) return;
+    for (size_t i = from; i < from + n && i < m->cfg.seq_len; i++) {
+        if (!kv.kv_vis_host[i]) {
+            kv.kv_vis_host[i] = 1;
+            kv.n_hidden--;
+            (void)hipMemcpyAsync(kv.kv_vis_dev + i, &kv.kv_vis_host[i], 1, hipMemcpyHostToDevice, m->ctx->stream);
+        }
+    }
+}
+// The one-launch attentions wait for each other's workgroups inside the launch (bounded); a wait that gave up raises
+// attn_sync[31].  Read it behind every synchronised single-token forward, clear it, and fall back to the two launches
+// from here on (mode bit 4): the forward that timed out has no valid result.  Expects the stream to be idle.
+// Every single-token forward that may have used the one-launch attention is followed, on the stream, by a 4-byte copy of the flag into pinned
+// host memory (note_single_token): looking at it costs no round trip once the stream is idle.
+int g_force_attn_timeout = 0; // ps_hip_debug_set(5, n): the next n single-token forwards on the one-launch attention report a time-out (tests of the retry paths)
+static void note_single_token(ps_hip_model *m) {
+    if (m->mode & 16) return; // the one-launch form is not in use
+    if (g_force_attn_timeout > 0) { g_force_attn_timeout--; (void)hipMemsetAsync(m->attn_sync + 31, 1, 1, m->ctx->stream); } // (word = 1, behind the forward's launches)
+    (void)hipMemcpyAsync(m->attn_flag_host, m->attn_sync + 31, 4, hipMemcpyDeviceToHost, m->ctx->stream);
+    m->attn_unchecked = true;
+}
+// 0: nothing pending or the flag is clear.  PS_HIP_ATTN_TIMEOUT (3): the forward(s) since the last check have no valid result; the model has
+// switched to the two-launch attention (mode bit 4, sticky; graphs dropped) and c->err says so -- the callers that still know their inputs run
+// them again, ONCE (behind the switch no forward can time out: note_single_token arms nothing under mode bit 4).  1: a HIP error (c->err),
+// never retried.  The switch happens before anything that can fail, so a failing memset cannot leave the one-launch form armed with its flag up.
+static int check_attn_timeout(ps_hip_model *m, const char *who) {
+    ps_hip_ctx *c = m->ctx;
+    if (!m->attn_unchecked) return 0;
+    m->attn_unchecked = false;
+    if (!*(volatile unsigned *)m->attn_flag_host) return 0;
+    *(volatile unsigned *)m->attn_flag_host = 0;
+    m->mode |= 16;
+    m->attn1_disabled = true;
+    drop_graphs(m);
+    PS_CHECK(c, hipMemset(m->attn_sync + 31, 0, 4));
+    c->err = std::string(who) + ": the one-launch attention timed out at its score exchange (GPU shared or partitioned?); this forward has no valid "
+             "result, the cache position is unchanged, and the model now uses the two-launch attention (mode bit 4)";
+    return PS_HIP_ATTN_TIMEOUT;
+}
+// The retry of every entry point that still knows its inputs: `run` enqueues, waits and ends in check_attn_timeout.  A time-out: the model is on the
+// two-launch attention now, the same work once more; any other code, and a second time-out, are the caller's.
+template <class F> static int with_attn_retry(ps_hip_model *m, F &&run) {
+    const int rc = run();
+    if (rc != PS_HIP_ATTN_TIMEOUT) return rc;
+    m->ctx->err.clear();
+    return run();
+}
+// A lowered forward that nobody has consumed yet (no kv_advance / sync_check since) must not leave its flag to the next, unrelated forward:
+// every entry point settles it first and hands a time-out back to the caller, who still owns that forward's inputs.
+static int settle_pending(ps_hip_model *m) {
+    if (!m->attn_unchecked) return 0;
+    return ps_hip_model_sync_check(m);
 }
 
 extern "C" {
@@ -376,11 +508,12 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
     if ((int)f.rope.n_dims != (int)f.head_size) PS_FAIL(c, "model_create: rope n_dims != head_size (reference asserts the same, norm_attention.cpp:38)");
     if (f.seq_len % 4) PS_FAIL(c, "model_create: n_ctx must be a multiple of 4");
     if ((size_t)(f.n_heads / f.n_kv_heads) * f.seq_len * 4 + 44 * 1024 > 158 * 1024) PS_FAIL(c, "model_create: n_ctx too large for the LDS-resident softmax rows (cap n_ctx)");
-    if (f.n_heads / f.n_kv_heads > 8) PS_FAIL(c, "model_create: more than 8 query heads per kv head");
     PS_CHECK(c, hipSetDevice(c->device));
     auto m = new ps_hip_model();
     m->ctx = c; m->cfg = f; m->qwen2 = d->is_qwen2 != 0; m->max_batch = d->max_batch > 0 ? d->max_batch : 1;
     m->mode = mode_env_or() & ~8; // (the fp16-KV mode allocates: only through set_mode)
+    m->seqs.resize(1);
+    ps_hip_model::seq_state &s0 = m->seqs[0];
     m->token_embd = d->token_embd; m->output = d->output; m->output_norm = d->output_norm;
     const uint32_t L = f.n_layers;
     auto cpf = [&](std::vector<const float *> &v, const float *const *src) { v.assign(L, nullptr); if (src) for (uint32_t i = 0; i < L; i++) v[i] = src[i]; };
@@ -408,7 +541,7 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
         dmalloc(m, &m->act_mem, ps_act_bytes(dim > hid ? dim : hid, mb)) ||
         dmalloc(m, (void **)&m->state, sizeof(ps_step_state)) || dmalloc(m, (void **)&m->state_sub, 64 * sizeof(ps_step_state)) || dmalloc(m, (void **)&m->tokens_dev, mb * 4) ||
         dmalloc(m, (void **)&m->argmax_dev, mb * 4) || dmalloc(m, (void **)&m->ids_dev, (nctx + 1) * 4) ||
-        dmalloc(m, (void **)&m->tree_dev, mb * mb) || dmalloc(m, (void **)&m->rope_pos_dev, mb * 4) || dmalloc(m, (void **)&m->kv_vis_dev, nctx) || dmalloc(m, (void **)&m->am_v, mb * 64 * 4) || dmalloc(m, (void **)&m->am_i, mb * 64 * 4))
+        dmalloc(m, (void **)&m->tree_dev, mb * mb) || dmalloc(m, (void **)&m->rope_pos_dev, mb * 4) || dmalloc(m, (void **)&s0.kv_vis_dev, nctx) || dmalloc(m, (void **)&m->am_v, mb * 64 * 4) || dmalloc(m, (void **)&m->am_i, mb * 64 * 4))
         return fail();
     {
         bool any16 = (m->output ? m->output : m->token_embd)->dtype == PS_F16;
@@ -423,13 +556,13 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
     m->pin_argmax = m->pin_tokens + mb;
     (void)hipMemsetAsync(m->attn_tick, 0, (size_t)f.n_kv_heads * 64 * 4, c->stream);
     (void)hipMemsetAsync(m->attn_gran, 0, (size_t)(f.n_heads + 2 * f.n_kv_heads) * f.head_size * 8, c->stream); // (tag 0: no launch's)
-    (void)hipMemsetAsync(m->kv_vis_dev, 1, nctx, c->stream);
-    m->kv_vis_host.assign(nctx, 1);
-    m->k_cache.assign(L, nullptr); m->v_cache.assign(L, nullptr);
+    (void)hipMemsetAsync(s0.kv_vis_dev, 1, nctx, c->stream);
+    s0.kv_vis_host.assign(nctx, 1);
+    s0.k_cache.assign(L, nullptr); s0.v_cache.assign(L, nullptr);
     for (uint32_t i = 0; i < L; i++) {
-        if (dmalloc(m, (void **)&m->k_cache[i], nctx * kvd * 4) || dmalloc(m, (void **)&m->v_cache[i], nctx * kvd * 4)) return fail();
-        (void)hipMemsetAsync(m->k_cache[i], 0, nctx * kvd * 4, c->stream);
-        (void)hipMemsetAsync(m->v_cache[i], 0, nctx * kvd * 4, c->stream);
+        if (dmalloc(m, (void **)&s0.k_cache[i], nctx * kvd * 4) || dmalloc(m, (void **)&s0.v_cache[i], nctx * kvd * 4)) return fail();
+        (void)hipMemsetAsync(s0.k_cache[i], 0, nctx * kvd * 4, c->stream);
+        (void)hipMemsetAsync(s0.v_cache[i], 0, nctx * kvd * 4, c->stream);
     }
     // RoPE table for every cache position, host-built with the reference recurrence
     std::vector<float> tab(nctx * f.head_size);
@@ -451,71 +584,61 @@ void ps_hip_model_destroy(ps_hip_model *m) {
     delete m;
 }
 
-size_t ps_hip_model_kv_position(const ps_hip_model *m) { return m->position; }
+size_t ps_hip_model_kv_position(const ps_hip_model *m) { return m->cur().position; }
 int ps_hip_model_max_batch(const ps_hip_model *m) { return m->max_batch; }
-static void unmask_range(ps_hip_model *m, size_t from, size_t n);
-extern "C" int ps_hip_model_sync_check(ps_hip_model *m);
-static int settle_pending(ps_hip_model *m);
 // slots at or behind the position are never consulted through the visibility table (the causal / tree mask governs them)
 // and KVCache::advance_tokens / append un-hides what it walks over (core/kv_cache.hpp:249-255): a rollback or truncate
 // leaves no hidden slot behind the new position, so a model that served as a speculative draft can decode again
 int ps_hip_model_kv_truncate(ps_hip_model *m, size_t n) {
     if (int rc = settle_pending(m)) return rc; // (every KV entry point: an unconsumed lowered forward's time-out belongs to ITS caller, not to the next forward)
-    if (n < m->position) m->position = n;
-    unmask_range(m, m->position, m->cfg.seq_len - m->position);
+    size_t &position = m->cur().position;
+    if (n < position) position = n;
+    unmask_range(m, position, m->cfg.seq_len - position);
     return 0;
-}
-// KVCache::advance_tokens unmasks the slots it walks over (core/kv_cache.hpp:249-255)
-static void unmask_range(ps_hip_model *m, size_t from, size_t n) {
-    if (!m->n_hidden) return;
-    for (size_t i = from; i < from + n && i < m->cfg.seq_len; i++) {
-        if (!m->kv_vis_host[i]) {
-            m->kv_vis_host[i] = 1;
-            m->n_hidden--;
-            (void)hipMemcpyAsync(m->kv_vis_dev + i, &m->kv_vis_host[i], 1, hipMemcpyHostToDevice, m->ctx->stream);
-        }
-    }
 }
 int ps_hip_model_kv_advance(ps_hip_model *m, size_t n) {
     if (int rc = ps_hip_model_sync_check(m)) return rc; // (an unsynchronised lowered forward: its rows must be valid before they count)
-    if (m->position + n > m->cfg.seq_len) { m->ctx->err = "kv_advance: KV cache is full (n_ctx)"; return 2; }
-    unmask_range(m, m->position, n);
-    m->position += n;
+    size_t &position = m->cur().position;
+    if (position + n > m->cfg.seq_len) { m->ctx->err = "kv_advance: KV cache is full (n_ctx)"; return 2; }
+    unmask_range(m, position, n);
+    position += n;
     return 0;
 }
 int ps_hip_model_kv_rollback(ps_hip_model *m, size_t n) {
     if (int rc = settle_pending(m)) return rc;
-    if (n > m->position) { m->ctx->err = "kv_rollback: more tokens than cached"; return 2; }
-    m->position -= n;
-    unmask_range(m, m->position, m->cfg.seq_len - m->position);
+    size_t &position = m->cur().position;
+    if (n > position) { m->ctx->err = "kv_rollback: more tokens than cached"; return 2; }
+    position -= n;
+    unmask_range(m, position, m->cfg.seq_len - position);
     return 0;
 }
 int ps_hip_model_kv_move(ps_hip_model *m, size_t dst, size_t src) {
     if (int rc = settle_pending(m)) return rc; // (rows of a forward whose result is invalid must not be copied)
     if (dst == src) return 0;
     if (dst >= m->cfg.seq_len || src >= m->cfg.seq_len) { m->ctx->err = "kv_move: index out of range"; return 2; }
+    const ps_hip_model::seq_state &kv = m->cur();
     for (uint32_t L = 0; L < m->cfg.n_layers; L++)
-        hipLaunchKernelGGL(kv_move_kernel, dim3((m->cfg.kv_dim + 255) / 256), dim3(256), 0, m->ctx->stream, m->k_cache[L],
-                           m->v_cache[L], m->k16.empty() ? nullptr : m->k16[L], m->v16.empty() ? nullptr : m->v16[L], (int)m->cfg.kv_dim, (int)m->cfg.seq_len, (int)dst, (int)src);
+        hipLaunchKernelGGL(kv_move_kernel, dim3((m->cfg.kv_dim + 255) / 256), dim3(256), 0, m->ctx->stream, kv.k_cache[L],
+                           kv.v_cache[L], m->k16.empty() ? nullptr : m->k16[L], m->v16.empty() ? nullptr : m->v16[L], (int)m->cfg.kv_dim, (int)m->cfg.seq_len, (int)dst, (int)src);
     return 0;
 }
 // ---- the rest of KVCacheInterface (core/kv_cache.hpp:120-162; see include/ps_hip.h for why they reduce to these)
 int ps_hip_model_kv_copy(ps_hip_model *m, size_t dst_cache_index, size_t src_token_index) {
-    return ps_hip_model_kv_move(m, dst_cache_index, m->position + src_token_index);
+    return ps_hip_model_kv_move(m, dst_cache_index, m->cur().position + src_token_index);
 }
 int ps_hip_model_kv_save_tokens(ps_hip_model *m, size_t n) {
     if (int rc = settle_pending(m)) return rc;
-    if (m->position + n > m->cfg.seq_len) { m->ctx->err = "kv_save_tokens: the length of kvcache is up to the preset threshold (n_ctx)"; return 2; }
+    if (m->cur().position + n > m->cfg.seq_len) { m->ctx->err = "kv_save_tokens: the length of kvcache is up to the preset threshold (n_ctx)"; return 2; }
     return 0;
 }
 int ps_hip_model_kv_unmask_tokens(ps_hip_model *m, size_t n) {
     if (int rc = settle_pending(m)) return rc;
-    if (m->position + n > m->cfg.seq_len) { m->ctx->err = "kv_unmask_tokens: the length of kvcache is up to the preset threshold (n_ctx)"; return 2; }
-    unmask_range(m, m->position, n);
+    if (m->cur().position + n > m->cfg.seq_len) { m->ctx->err = "kv_unmask_tokens: the length of kvcache is up to the preset threshold (n_ctx)"; return 2; }
+    unmask_range(m, m->cur().position, n);
     return 0;
 }
 int ps_hip_model_kv_append_tokens(ps_hip_model *m, size_t n, size_t *old_position) {
-    const size_t old = m->position;
+    const size_t old = m->cur().position;
     if (int rc = ps_hip_model_kv_save_tokens(m, n)) return rc;
     if (int rc = ps_hip_model_kv_unmask_tokens(m, n)) return rc;
     if (int rc = ps_hip_model_kv_advance(m, n)) return rc;
@@ -523,213 +646,143 @@ int ps_hip_model_kv_append_tokens(ps_hip_model *m, size_t n, size_t *old_positio
     return 0;
 }
 
-static int model_forward_impl(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *pos, const uint8_t *tree, int lm_head,
-                              int32_t *argmax_host, bool advance, bool retried = false);
-// The one-launch attentions wait for each other's workgroups inside the launch (bounded); a wait that gave up raises
-// attn_sync[31].  Read it behind every synchronised single-token forward, clear it, and fall back to the two launches
-// from here on (mode bit 4): the forward that timed out has no valid result.  Expects the stream to be idle.
-static void drop_graphs(ps_hip_model *m) { // every captured launch plan (they bake the mode, the prefetch hint and the visibility pointers in)
-    if (m->step_graph) { (void)hipGraphExecDestroy(m->step_graph); m->step_graph = nullptr; }
-    if (m->sample_graph) { (void)hipGraphExecDestroy(m->sample_graph); m->sample_graph = nullptr; }
-    for (auto &g : m->fwd1_graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-}
-// Every single-token forward that may have used the one-launch attention is followed, on the stream, by a 4-byte copy of the flag into pinned
-// host memory (note_single_token): looking at it costs no round trip once the stream is idle.
-int g_force_attn_timeout = 0; // ps_hip_debug_set(5, n): the next n single-token forwards on the one-launch attention report a time-out (tests of the retry paths)
-static void note_single_token(ps_hip_model *m) {
-    if (m->mode & 16) return; // the one-launch form is not in use
-    if (g_force_attn_timeout > 0) { g_force_attn_timeout--; (void)hipMemsetAsync(m->attn_sync + 31, 1, 1, m->ctx->stream); } // (word = 1, behind the forward's launches)
-    (void)hipMemcpyAsync(m->attn_flag_host, m->attn_sync + 31, 4, hipMemcpyDeviceToHost, m->ctx->stream);
-    m->attn_unchecked = true;
-}
-// 0: nothing pending or the flag is clear.  PS_HIP_ATTN_TIMEOUT (3): the forward(s) since the last check have no valid result; the model has
-// switched to the two-launch attention (mode bit 4, sticky; graphs dropped) and c->err says so -- the callers that still know their inputs run
-// them again, ONCE (behind the switch no forward can time out: note_single_token arms nothing under mode bit 4).  1: a HIP error (c->err),
-// never retried.  The switch happens before anything that can fail, so a failing memset cannot leave the one-launch form armed with its flag up.
-static int check_attn_timeout(ps_hip_model *m, const char *who) {
-    ps_hip_ctx *c = m->ctx;
-    if (!m->attn_unchecked) return 0;
-    m->attn_unchecked = false;
-    if (!*(volatile unsigned *)m->attn_flag_host) return 0;
-    *(volatile unsigned *)m->attn_flag_host = 0;
-    m->mode |= 16;
-    m->attn1_disabled = true;
-    drop_graphs(m);
-    PS_CHECK(c, hipMemset(m->attn_sync + 31, 0, 4));
-    c->err = std::string(who) + ": the one-launch attention timed out at its score exchange (GPU shared or partitioned?); this forward has no valid "
-             "result, the cache position is unchanged, and the model now uses the two-launch attention (mode bit 4)";
-    return PS_HIP_ATTN_TIMEOUT;
-}
-// A lowered forward that nobody has consumed yet (no kv_advance / sync_check since) must not leave its flag to the next, unrelated forward:
-// every entry point settles it first and hands a time-out back to the caller, who still owns that forward's inputs.
-static int settle_pending(ps_hip_model *m) {
-    if (!m->attn_unchecked) return 0;
-    return ps_hip_model_sync_check(m);
-}
 // The lowered op-API path (ps_hip_model_forward_lowered) returns before its launches have run: whoever consumes its result next -- the
 // cache advance (LlamaModel::forward advances right behind Executor::run, llama_model.cpp:109) or a logits read -- looks at the flag.
 int ps_hip_model_sync_check(ps_hip_model *m) {
     ps_hip_ctx *c = m->ctx;
     if (!m->attn_unchecked) return 0;
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    m->pin_busy = false; m->pin_argmax_pending = false; // (everything enqueued before this point has run)
+    PS_CHECK(c, sync_stream(m));
     return check_attn_timeout(m, "lowered forward");
 }
-int ps_hip_model_forward(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *pos, const uint8_t *tree, int lm_head,
-                         int32_t *argmax_host) {
-    return model_forward_impl(m, tokens, n, pos, tree, lm_head, argmax_host, true);
-}
-int ps_hip_model_forward_lowered(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *pos, const uint8_t *tree, int lm_head) {
-    return model_forward_impl(m, tokens, n, pos, tree, lm_head, nullptr, false);
-}
-static int model_forward_impl(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *pos, const uint8_t *tree, int lm_head,
-                              int32_t *argmax_host, bool advance, bool retried) {
+static int model_forward(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *pos, const uint8_t *tree, int lm_head,
+                         int32_t *argmax_host, bool advance) {
     ps_hip_ctx *c = m->ctx;
     if (int rc = settle_pending(m)) return rc;
     if (n <= 0 || n > m->max_batch) PS_FAIL(c, "model_forward: batch size out of range");
     for (int i = 1; i < n; i++)
         if (pos[i] != pos[0] + i) PS_FAIL(c, "model_forward: positions must be consecutive (KV append is one contiguous copy, norm_attention.cpp:82-91)");
     if (pos[0] < 0 || (size_t)pos[0] + (size_t)n > m->cfg.seq_len) PS_FAIL(c, "model_forward: KV cache is full (n_ctx)");
-    for (int i = 0; i < n; i++)
-        if (tokens[i] < 0 || (uint32_t)tokens[i] >= m->cfg.vocab_size) PS_FAIL(c, "model_forward: token id out of range");
-    PS_CHECK(c, hipSetDevice(c->device));
-    m->pin_argmax_n = 0; // (the arg-max ids on the device are about to change)
-    if (n == 1 && !tree) { // a decode step: the token travels from a pinned word, nothing to wait for before the launches go out
-        if (m->pin_busy) { PS_CHECK(c, hipStreamSynchronize(c->stream)); m->pin_busy = false; m->pin_argmax_pending = false; } // (an upload from that word may still be queued)
-        m->pin_tokens[0] = tokens[0];
-        PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, m->pin_tokens, 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, pos[0], n, 0);
-        m->pin_busy = true;
-    } else {
-        PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        if (tree) PS_CHECK(c, hipMemcpyAsync(m->tree_dev, tree, (size_t)n * n, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, pos[0], n, 0);
-        PS_CHECK(c, hipStreamSynchronize(c->stream)); // tokens/tree may be host temporaries
-        m->pin_busy = false; m->pin_argmax_pending = false;
-    }
-    // A single token through this entry (ModelTokenIterator::decode over the op API, HIPBackend::plan's lowered graph) replays
-    // a captured launch plan like ps_hip_model_decode_greedy does: the first call at a position range runs eagerly and captures.
-    const int gk = lm_head ? 1 : 0;
-    const bool graphable = n == 1 && !tree && (m->mode & 1) == 0 && m->n_hidden == 0;
-    if (graphable && m->fwd1_graph[gk] && ((size_t)pos[0] < m->fwd1_hint[gk] || (size_t)pos[0] >= m->fwd1_hint[gk] + 1024)) {
-        (void)hipGraphExecDestroy(m->fwd1_graph[gk]); m->fwd1_graph[gk] = nullptr;
-    }
-    if (graphable && m->fwd1_graph[gk]) {
-        PS_CHECK(c, hipGraphLaunch(m->fwd1_graph[gk], c->stream));
-    } else {
-        m->n_kv_host = pos[0] + n;
-        const int rc_fw = enqueue_forward(m, n, lm_head != 0, tree != nullptr);
-        if (rc_fw) { m->n_kv_host = 0; return rc_fw; }
-        if (graphable) { // capture the same launches (nothing executes); the hint stays a lower bound of n_kv for 1024 positions
-            hipGraph_t g = nullptr;
-            PS_CHECK(c, hipStreamSynchronize(c->stream));
-            m->n_kv_host = 0; m->n_kv_hint = pos[0]; // (no host-side n_kv inside a graph: the score grids cover n_ctx)
-            PS_CHECK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            const int rc = enqueue_forward(m, 1, lm_head != 0, false);
-            const hipError_t e = hipStreamEndCapture(c->stream, &g);
-            m->n_kv_hint = 0;
-            if (!rc && e == hipSuccess && hipGraphInstantiate(&m->fwd1_graph[gk], g, nullptr, nullptr, 0) == hipSuccess) m->fwd1_hint[gk] = (size_t)pos[0];
-            else m->fwd1_graph[gk] = nullptr; // (stay eager)
-            if (g) (void)hipGraphDestroy(g);
+    if (int rc = check_tokens(m, tokens, n, "model_forward")) return rc;
+    return with_attn_retry(m, [&]() -> int {
+        PS_CHECK(c, hipSetDevice(c->device));
+        m->pin_argmax_n = 0; // (the arg-max ids on the device are about to change)
+        if (n == 1 && !tree) { // a decode step: the token travels from a pinned word, nothing to wait for before the launches go out
+            if (m->pin_busy) PS_CHECK(c, sync_stream(m)); // (an upload from that word may still be queued)
+            m->pin_tokens[0] = tokens[0];
+            PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, m->pin_tokens, 4, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, pos[0], n, 0);
+            m->pin_busy = true;
+        } else {
+            PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            if (tree) PS_CHECK(c, hipMemcpyAsync(m->tree_dev, tree, (size_t)n * n, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, pos[0], n, 0);
+            PS_CHECK(c, sync_stream(m)); // tokens/tree may be host temporaries
         }
-        m->n_kv_host = 0;
-    }
-    if (n == 1 && !tree) note_single_token(m);
-    if (lm_head && argmax_host) PS_CHECK(c, hipMemcpyAsync(argmax_host, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (lm_head && !advance) { // lowered graph: the ids ride to pinned memory behind the launches; ps_hip_model_argmax finds them there after the cache advance's wait
-        PS_CHECK(c, hipMemcpyAsync(m->pin_argmax, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        m->pin_argmax_n = n; m->pin_argmax_pending = true;
-    }
-    if (!advance) return 0; // lowered graph: ps_hip_model_kv_advance / ps_hip_model_sync_check look at the time-out flag before the result counts
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    m->pin_busy = false; m->pin_argmax_pending = false;
-    if (const int rc = check_attn_timeout(m, "model_forward")) { // a time-out: the model is on the two-launch attention now, the same forward once more (inputs are the caller's)
-        if (rc != PS_HIP_ATTN_TIMEOUT || retried) return rc;
-        c->err.clear();
-        return model_forward_impl(m, tokens, n, pos, tree, lm_head, argmax_host, advance, true);
-    }
-    unmask_range(m, (size_t)pos[0], (size_t)n);
-    m->position = (size_t)pos[0] + (size_t)n; // m_kv->advance (llama_model.cpp:109)
-    return 0;
+        // A single token through this entry (ModelTokenIterator::decode over the op API, HIPBackend::plan's lowered graph) replays
+        // a captured launch plan like ps_hip_model_decode_greedy does: the first call at a position range runs eagerly and captures.
+        step_graph &g = m->graphs[lm_head ? G_FWD1_LM : G_FWD1];
+        const bool graphable = n == 1 && !tree && (m->mode & 1) == 0 && m->cur().n_hidden == 0;
+        if (graphable) graph_drop_if_stale(g, (size_t)pos[0]);
+        if (graphable && g.exec) {
+            PS_CHECK(c, hipGraphLaunch(g.exec, c->stream));
+        } else {
+            fwd_opts o;
+            o.lm_head = lm_head != 0; o.tree = tree != nullptr; o.n_kv_host = pos[0] + n;
+            if (int rc = enqueue_forward(m, n, o)) return rc;
+            if (graphable) { // capture the same launches (nothing executes); the hint stays a lower bound of n_kv for 1024 positions
+                PS_CHECK(c, sync_stream(m));
+                o.n_kv_host = 0; o.n_kv_hint = pos[0]; // (no host-side n_kv inside a graph: the score grids cover n_ctx)
+                (void)graph_capture(m, g, (size_t)pos[0], [&] { return enqueue_forward(m, 1, o); }); // (a failure: stay eager)
+            }
+        }
+        if (n == 1 && !tree) note_single_token(m);
+        if (lm_head && argmax_host) PS_CHECK(c, hipMemcpyAsync(argmax_host, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (lm_head && !advance) { // lowered graph: the ids ride to pinned memory behind the launches; ps_hip_model_argmax finds them there after the cache advance's wait
+            PS_CHECK(c, hipMemcpyAsync(m->pin_argmax, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+            m->pin_argmax_n = n; m->pin_argmax_pending = true;
+        }
+        if (!advance) return 0; // lowered graph: ps_hip_model_kv_advance / ps_hip_model_sync_check look at the time-out flag before the result counts
+        PS_CHECK(c, sync_stream(m));
+        if (const int rc = check_attn_timeout(m, "model_forward")) return rc; // (a time-out: the same forward once more, the inputs are the caller's)
+        unmask_range(m, (size_t)pos[0], (size_t)n);
+        m->cur().position = (size_t)pos[0] + (size_t)n; // m_kv->advance (llama_model.cpp:109)
+        return 0;
+    });
+}
+int ps_hip_model_forward(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *pos, const uint8_t *tree, int lm_head,
+                         int32_t *argmax_host) {
+    return model_forward(m, tokens, n, pos, tree, lm_head, argmax_host, true);
+}
+int ps_hip_model_forward_lowered(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *pos, const uint8_t *tree, int lm_head) {
+    return model_forward(m, tokens, n, pos, tree, lm_head, nullptr, false);
 }
 
 // ModelTokenIterator's prefill (src/model/model.hpp:147-163): forward(tokens[done .. done + chunk), lm_head = false) chunk after chunk, the
 // cache advanced after each -- with the SAME bits, but up to max_batch / chunk reference chunks per launch sequence ("super-chunk"): every
 // mat-mul of a layer sees all their columns at once (per-chunk fixed costs paid a quarter as often at chunk 128 / max_batch 512), only the
-// attention is evaluated per reference chunk (ps_hip_model::attn_chunk).  8B, chunk 128: 14.4 k -> ~17 k tok/s.
+// attention is evaluated per reference chunk (fwd_opts::attn_chunk).  8B, chunk 128: 14.4 k -> ~17 k tok/s.
 int ps_hip_model_prefill(ps_hip_model *m, const int32_t *tokens, int n, int chunk) {
     ps_hip_ctx *c = m->ctx;
     if (n <= 0) return 0;
     if (int rc = settle_pending(m)) return rc;
     if (chunk <= 0 || chunk > m->max_batch) PS_FAIL(c, "model_prefill: chunk size out of range");
-    if (m->position + (size_t)n > m->cfg.seq_len) PS_FAIL(c, "model_prefill: KV cache is full (n_ctx)");
-    for (int i = 0; i < n; i++)
-        if (tokens[i] < 0 || (uint32_t)tokens[i] >= m->cfg.vocab_size) PS_FAIL(c, "model_prefill: token id out of range");
+    if (m->cur().position + (size_t)n > m->cfg.seq_len) PS_FAIL(c, "model_prefill: KV cache is full (n_ctx)");
+    if (int rc = check_tokens(m, tokens, n, "model_prefill")) return rc;
     PS_CHECK(c, hipSetDevice(c->device));
     m->pin_argmax_n = 0;
     int per = m->max_batch / chunk; // reference chunks per super-chunk
     if (per > 64) per = 64;
     if (per < 1) per = 1;
-    bool retried = false;
     for (int done = 0; done < n;) {
         const int ns = n - done < per * chunk ? n - done : per * chunk;
-        PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens + done, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, (int)m->position, ns, 0);
-        hipLaunchKernelGGL(set_sub_states_kernel, dim3(1), dim3(64), 0, c->stream, m->state_sub, (int)m->position, chunk, ns);
-        m->n_kv_host = (int)m->position + ns;
-        m->attn_chunk = chunk;
-        const int rc = enqueue_forward(m, ns, false, false);
-        m->attn_chunk = 0; m->n_kv_host = 0;
+        const int pos = (int)m->cur().position;
+        const int rc = with_attn_retry(m, [&]() -> int { // (per super-chunk: the ones before it have advanced the position)
+            PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens + done, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, pos, ns, 0);
+            hipLaunchKernelGGL(set_sub_states_kernel, dim3(1), dim3(64), 0, c->stream, m->state_sub, pos, chunk, ns);
+            fwd_opts o;
+            o.n_kv_host = pos + ns; o.attn_chunk = chunk;
+            if (int rc_fw = enqueue_forward(m, ns, o)) return rc_fw;
+            if (ns == 1) note_single_token(m);
+            PS_CHECK(c, sync_stream(m));
+            return check_attn_timeout(m, "model_prefill"); // a one-token tail: once more, with the two launches
+        });
         if (rc) return rc;
-        if (ns == 1) note_single_token(m);
-        PS_CHECK(c, hipStreamSynchronize(c->stream));
-        if (const int rc = check_attn_timeout(m, "model_prefill")) { // a one-token tail: once more, with the two launches
-            if (rc != PS_HIP_ATTN_TIMEOUT || retried) return rc;
-            retried = true; c->err.clear(); continue;
-        }
-        unmask_range(m, m->position, (size_t)ns);
-        m->position += (size_t)ns;
+        unmask_range(m, (size_t)pos, (size_t)ns);
+        m->cur().position += (size_t)ns;
         done += ns;
     }
     return 0;
 }
 
-static int forward_tree_impl(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *rope_pos, const uint8_t *tree, int lm_head,
-                             int32_t *argmax_host, int advance, bool retried);
 int ps_hip_model_forward_tree(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *rope_pos, const uint8_t *tree, int lm_head,
                               int32_t *argmax_host, int advance) {
-    return forward_tree_impl(m, tokens, n, rope_pos, tree, lm_head, argmax_host, advance, false);
-}
-static int forward_tree_impl(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *rope_pos, const uint8_t *tree, int lm_head,
-                             int32_t *argmax_host, int advance, bool retried) {
     ps_hip_ctx *c = m->ctx;
     if (int rc = settle_pending(m)) return rc;
+    const size_t position = m->cur().position;
     if (n <= 0 || n > m->max_batch) PS_FAIL(c, "model_forward_tree: batch size out of range");
-    if (m->position + (size_t)n > m->cfg.seq_len) PS_FAIL(c, "model_forward_tree: KV cache is full (n_ctx)");
-    for (int i = 0; i < n; i++) {
-        if (tokens[i] < 0 || (uint32_t)tokens[i] >= m->cfg.vocab_size) PS_FAIL(c, "model_forward_tree: token id out of range");
+    if (position + (size_t)n > m->cfg.seq_len) PS_FAIL(c, "model_forward_tree: KV cache is full (n_ctx)");
+    if (int rc = check_tokens(m, tokens, n, "model_forward_tree")) return rc;
+    for (int i = 0; i < n; i++)
         if (rope_pos[i] < 0 || (uint32_t)rope_pos[i] >= m->cfg.seq_len) PS_FAIL(c, "model_forward_tree: position out of range");
-    }
-    PS_CHECK(c, hipSetDevice(c->device));
-    m->pin_argmax_n = 0;
-    PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    PS_CHECK(c, hipMemcpyAsync(m->rope_pos_dev, rope_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    if (tree) PS_CHECK(c, hipMemcpyAsync(m->tree_dev, tree, (size_t)n * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, (int)m->position, n, 0);
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    m->n_kv_host = (int)m->position + n;
-    const int rc_fw = enqueue_forward(m, n, lm_head != 0, tree != nullptr, false, true);
-    m->n_kv_host = 0;
-    if (rc_fw) return rc_fw;
-    if (n == 1 && !tree) note_single_token(m);
-    if (lm_head && argmax_host) PS_CHECK(c, hipMemcpyAsync(argmax_host, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    if (const int rc = check_attn_timeout(m, "model_forward_tree")) {
-        if (rc != PS_HIP_ATTN_TIMEOUT || retried) return rc;
-        c->err.clear();
-        return forward_tree_impl(m, tokens, n, rope_pos, tree, lm_head, argmax_host, advance, true);
-    }
-    if (advance) { unmask_range(m, m->position, (size_t)n); m->position += (size_t)n; }
+    const int rc = with_attn_retry(m, [&]() -> int {
+        PS_CHECK(c, hipSetDevice(c->device));
+        m->pin_argmax_n = 0;
+        PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        PS_CHECK(c, hipMemcpyAsync(m->rope_pos_dev, rope_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        if (tree) PS_CHECK(c, hipMemcpyAsync(m->tree_dev, tree, (size_t)n * n, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, (int)position, n, 0);
+        PS_CHECK(c, sync_stream(m));
+        fwd_opts o;
+        o.lm_head = lm_head != 0; o.tree = tree != nullptr; o.rope_pos = true; o.n_kv_host = (int)position + n;
+        if (int rc_fw = enqueue_forward(m, n, o)) return rc_fw;
+        if (n == 1 && !tree) note_single_token(m);
+        if (lm_head && argmax_host) PS_CHECK(c, hipMemcpyAsync(argmax_host, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        PS_CHECK(c, sync_stream(m));
+        return check_attn_timeout(m, "model_forward_tree");
+    });
+    if (rc) return rc;
+    if (advance) { unmask_range(m, position, (size_t)n); m->cur().position += (size_t)n; }
     return 0;
 }
 
@@ -737,145 +790,93 @@ int ps_hip_model_kv_mask(ps_hip_model *m, size_t index, int visible) {
     ps_hip_ctx *c = m->ctx;
     if (int rc = settle_pending(m)) return rc;
     if (index >= m->cfg.seq_len) PS_FAIL(c, "kv_mask: index out of range");
+    ps_hip_model::seq_state &kv = m->cur();
     const uint8_t v = visible ? 1 : 0;
-    if (m->kv_vis_host[index] == v) return 0;
-    m->kv_vis_host[index] = v;
-    if (v) m->n_hidden--; else m->n_hidden++;
-    PS_CHECK(c, hipMemcpyAsync(m->kv_vis_dev + index, &m->kv_vis_host[index], 1, hipMemcpyHostToDevice, c->stream));
+    if (kv.kv_vis_host[index] == v) return 0;
+    kv.kv_vis_host[index] = v;
+    if (v) kv.n_hidden--; else kv.n_hidden++;
+    PS_CHECK(c, hipMemcpyAsync(kv.kv_vis_dev + index, &kv.kv_vis_host[index], 1, hipMemcpyHostToDevice, c->stream));
     return 0;
 }
 
-static int decode_greedy_impl(ps_hip_model *m, int32_t token, int steps, int32_t *out_ids, bool retried);
-int ps_hip_model_decode_greedy(ps_hip_model *m, int32_t token, int steps, int32_t *out_ids) { return decode_greedy_impl(m, token, steps, out_ids, false); }
-static int decode_greedy_impl(ps_hip_model *m, int32_t token, int steps, int32_t *out_ids, bool retried) {
+// `steps` single-token steps, each fed the id the one before it chose: the arg-max (ps_hip_model_decode_greedy, cfg == nullptr), or the sampler chain in
+// its place (ps_hip_model_decode_sampled, k_sample.hip): the configuration and the engine go to the device once per run, the engine comes back at the end.
+// A time-out retry starts again from the caller's state, which is untouched until success.
+static int decode_run(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids) {
     ps_hip_ctx *c = m->ctx;
+    const char *who = cfg ? "decode_sampled" : "decode_greedy";
+    const std::string w = std::string(who) + ": ";
     if (steps <= 0) return 0;
     if (int rc = settle_pending(m)) return rc;
-    if (m->n_hidden) PS_FAIL(c, "decode_greedy: hidden KV slots (kv_mask) are not part of the captured step; unmask first");
-    if (m->position + (size_t)steps > m->cfg.seq_len) PS_FAIL(c, "decode_greedy: KV cache would overflow n_ctx");
-    if (token < 0 || (uint32_t)token >= m->cfg.vocab_size) PS_FAIL(c, "decode_greedy: token id out of range");
-    PS_CHECK(c, hipSetDevice(c->device));
-    m->pin_argmax_n = 0;
-    PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, &token, 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, (int)m->position, 1, 0);
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    int s = 0;
-    // the captured step carries the position it was captured at as a prefetch hint (n_kv_lo): keep it a LOWER bound that
-    // is not far behind (a stale hint costs time, never results)
-    if (m->step_graph && (m->position < m->graph_hint || m->position >= m->graph_hint + 1024)) { (void)hipGraphExecDestroy(m->step_graph); m->step_graph = nullptr; }
-    if ((m->mode & 1) == 0 && !m->step_graph) {
-        // first step runs eagerly (also performs every one-time hipFuncSetAttribute), then the identical
-        // launch sequence is captured; capture itself executes nothing
-        if (int rc = enqueue_forward(m, 1, true, false, true)) return rc;
-        PS_CHECK(c, hipStreamSynchronize(c->stream));
-        s = 1;
-        hipGraph_t g = nullptr;
-        m->graph_hint = m->position;
-        PS_CHECK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_forward(m, 1, true, false, true);
-        hipError_t e = hipStreamEndCapture(c->stream, &g);
-        if (rc || e != hipSuccess) { c->err = "decode_greedy: graph capture failed: " + c->err; if (g) (void)hipGraphDestroy(g); return 2; }
-        PS_CHECK(c, hipGraphInstantiate(&m->step_graph, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-    }
-    for (; s < steps; s++) {
-        if ((m->mode & 1) == 0) {
-            PS_CHECK(c, hipGraphLaunch(m->step_graph, c->stream));
-        } else {
-            if (int rc = enqueue_forward(m, 1, true, false, true)) return rc;
+    if (m->cur().n_hidden) PS_FAIL(c, w + "hidden KV slots (kv_mask) are not part of the captured step; unmask first");
+    if (m->cur().position + (size_t)steps > m->cfg.seq_len) PS_FAIL(c, w + "KV cache would overflow n_ctx");
+    if (int rc = check_tokens(m, &token, 1, who)) return rc;
+    fwd_opts step;
+    step.lm_head = true; step.advance = true; step.sampled = cfg != nullptr;
+    step_graph &g = m->graphs[cfg ? G_SAMPLED : G_GREEDY];
+    ps_sample_dev h; // (staging of the sampler's upload / read-back; the stream is idle between the two)
+    return with_attn_retry(m, [&]() -> int {
+        const size_t position = m->cur().position;
+        if (cfg) {
+            std::string err;
+            if (psl_sample_pack(cfg, state, (int)m->cfg.vocab_size, &h, &err)) { c->err = w + err; return 2; }
         }
-    }
-    note_single_token(m);
-    PS_CHECK(c, hipMemcpyAsync(out_ids, m->ids_dev, (size_t)steps * 4, hipMemcpyDeviceToHost, c->stream));
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    // a time-out anywhere in the run: the position has not moved and the first token is the caller's -- the whole run once more on the
-    // two-launch attention (every cache row it wrote is written again with the same values)
-    if (const int rc = check_attn_timeout(m, "decode_greedy")) {
-        if (rc != PS_HIP_ATTN_TIMEOUT || retried) return rc;
-        c->err.clear();
-        return decode_greedy_impl(m, token, steps, out_ids, true);
-    }
-    m->position += (size_t)steps;
-    return 0;
+        PS_CHECK(c, hipSetDevice(c->device));
+        if (cfg && !m->sample_dev && (dmalloc(m, (void **)&m->sample_dev, sizeof(ps_sample_dev)) || dmalloc(m, &m->sample_scratch, psl_sample_scratch_bytes((int)m->cfg.vocab_size)))) return 1;
+        m->pin_argmax_n = 0;
+        if (cfg) PS_CHECK(c, hipMemcpyAsync(m->sample_dev, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+        PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, &token, 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, (int)position, 1, 0);
+        PS_CHECK(c, sync_stream(m));
+        int s = 0;
+        graph_drop_if_stale(g, position);
+        if ((m->mode & 1) == 0 && !g.exec) {
+            // first step runs eagerly (also performs every one-time hipFuncSetAttribute), then the identical
+            // launch sequence is captured; capture itself executes nothing
+            if (int rc = enqueue_forward(m, 1, step)) return rc;
+            PS_CHECK(c, sync_stream(m));
+            s = 1;
+            if (!graph_capture(m, g, position, [&] { return enqueue_forward(m, 1, step); })) { c->err.insert(0, w + "graph capture failed: "); return 2; }
+        }
+        for (; s < steps; s++) {
+            if ((m->mode & 1) == 0) {
+                PS_CHECK(c, hipGraphLaunch(g.exec, c->stream));
+            } else {
+                if (int rc = enqueue_forward(m, 1, step)) return rc;
+            }
+        }
+        note_single_token(m);
+        PS_CHECK(c, hipMemcpyAsync(out_ids, m->ids_dev, (size_t)steps * 4, hipMemcpyDeviceToHost, c->stream));
+        if (cfg) PS_CHECK(c, hipMemcpyAsync(&h, m->sample_dev, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        PS_CHECK(c, sync_stream(m));
+        // a time-out anywhere in the run: the position has not moved and the first token is the caller's -- the whole run once more on the
+        // two-launch attention (every cache row it wrote is written again with the same values)
+        if (const int rc = check_attn_timeout(m, who)) return rc;
+        if (cfg) psl_sample_unpack(&h, state);
+        m->cur().position += (size_t)steps;
+        return 0;
+    });
 }
-
-// The greedy loop with the sampler chain in place of the arg-max (k_sample.hip): the configuration and the engine go to the device
-// once per run, the engine comes back at the end.  A time-out retry starts again from the caller's state, which is untouched until success.
-static int decode_sampled_impl(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids, bool retried);
+int ps_hip_model_decode_greedy(ps_hip_model *m, int32_t token, int steps, int32_t *out_ids) { return decode_run(m, token, steps, nullptr, nullptr, out_ids); }
 int ps_hip_model_decode_sampled(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids) {
-    return decode_sampled_impl(m, token, steps, cfg, state, out_ids, false);
-}
-static int decode_sampled_impl(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids, bool retried) {
-    ps_hip_ctx *c = m->ctx;
-    if (steps <= 0) return 0;
-    if (int rc = settle_pending(m)) return rc;
-    if (m->n_hidden) PS_FAIL(c, "decode_sampled: hidden KV slots (kv_mask) are not part of the captured step; unmask first");
-    if (m->position + (size_t)steps > m->cfg.seq_len) PS_FAIL(c, "decode_sampled: KV cache would overflow n_ctx");
-    if (token < 0 || (uint32_t)token >= m->cfg.vocab_size) PS_FAIL(c, "decode_sampled: token id out of range");
-    static ps_sample_dev h; // (staging of the upload / read-back; the stream is idle between the two)
-    {
-        std::string err;
-        if (psl_sample_pack(cfg, state, (int)m->cfg.vocab_size, &h, &err)) { c->err = "decode_sampled: " + err; return 2; }
-    }
-    PS_CHECK(c, hipSetDevice(c->device));
-    if (!m->sample_dev && (dmalloc(m, (void **)&m->sample_dev, sizeof(ps_sample_dev)) || dmalloc(m, &m->sample_scratch, psl_sample_scratch_bytes((int)m->cfg.vocab_size)))) return 1;
-    m->pin_argmax_n = 0;
-    PS_CHECK(c, hipMemcpyAsync(m->sample_dev, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-    PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, &token, 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, (int)m->position, 1, 0);
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    int s = 0;
-    if (m->sample_graph && (m->position < m->sample_hint || m->position >= m->sample_hint + 1024)) { (void)hipGraphExecDestroy(m->sample_graph); m->sample_graph = nullptr; }
-    if ((m->mode & 1) == 0 && !m->sample_graph) {
-        if (int rc = enqueue_forward(m, 1, true, false, true, false, true)) return rc;
-        PS_CHECK(c, hipStreamSynchronize(c->stream));
-        s = 1;
-        hipGraph_t g = nullptr;
-        m->sample_hint = m->position;
-        PS_CHECK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_forward(m, 1, true, false, true, false, true);
-        hipError_t e = hipStreamEndCapture(c->stream, &g);
-        if (rc || e != hipSuccess) { c->err = "decode_sampled: graph capture failed: " + c->err; if (g) (void)hipGraphDestroy(g); return 2; }
-        PS_CHECK(c, hipGraphInstantiate(&m->sample_graph, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-    }
-    for (; s < steps; s++) {
-        if ((m->mode & 1) == 0) {
-            PS_CHECK(c, hipGraphLaunch(m->sample_graph, c->stream));
-        } else {
-            if (int rc = enqueue_forward(m, 1, true, false, true, false, true)) return rc;
-        }
-    }
-    note_single_token(m);
-    PS_CHECK(c, hipMemcpyAsync(out_ids, m->ids_dev, (size_t)steps * 4, hipMemcpyDeviceToHost, c->stream));
-    PS_CHECK(c, hipMemcpyAsync(&h, m->sample_dev, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    if (const int rc = check_attn_timeout(m, "decode_sampled")) {
-        if (rc != PS_HIP_ATTN_TIMEOUT || retried) return rc;
-        c->err.clear();
-        return decode_sampled_impl(m, token, steps, cfg, state, out_ids, true);
-    }
-    psl_sample_unpack(&h, state);
-    m->position += (size_t)steps;
-    return 0;
+    return decode_run(m, token, steps, cfg, state, out_ids);
 }
 
 // ---- sequences: several KV caches (and positions, and visibility tables) on one model; include/ps_hip.h "Sequences"
-int ps_hip_model_seq_count(const ps_hip_model *m) { return m->seqs.empty() ? 1 : (int)m->seqs.size(); }
+int ps_hip_model_seq_count(const ps_hip_model *m) { return (int)m->seqs.size(); }
 size_t ps_hip_model_seq_position(const ps_hip_model *m, int s) {
-    if (s < 0 || s >= ps_hip_model_seq_count(m)) return (size_t)-1;
-    return s == m->cur_seq ? m->position : m->seqs[s].position;
+    if (s < 0 || s >= (int)m->seqs.size()) return (size_t)-1;
+    return m->seqs[s].position;
 }
-static size_t seq_hidden(const ps_hip_model *m, int s) { return s == m->cur_seq ? m->n_hidden : m->seqs[s].n_hidden; }
 // the model holds n_seq sequences and the batched step's tables.  Everything new is allocated before anything of the model changes: a failure (1) leaves it as it was.
 static int seq_grow(ps_hip_model *m, int n_seq) {
     ps_hip_ctx *c = m->ctx;
-    const int have = ps_hip_model_seq_count(m);
+    const int have = (int)m->seqs.size();
     if (n_seq < have) n_seq = have;
-    if (!m->seqs.empty() && n_seq == have) return 0;
+    if (m->seq_kv_dev && n_seq == have) return 0;
     const size_t L = m->cfg.n_layers, nctx = m->cfg.seq_len, cache_bytes = nctx * m->cfg.kv_dim * 4;
     PS_CHECK(c, hipSetDevice(c->device));
-    PS_CHECK(c, hipStreamSynchronize(c->stream)); // (the table in use is about to be replaced)
+    PS_CHECK(c, sync_stream(m)); // (the table in use is about to be replaced)
     std::vector<void *> fresh;
     auto grab = [&](void **p, size_t bytes) {
         if (ps_dev_malloc(p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); return 1; }
@@ -905,13 +906,14 @@ static int seq_grow(ps_hip_model *m, int n_seq) {
         (void)hipMemsetAsync(q.kv_vis_dev, 1, nctx, c->stream);
     }
     std::vector<float *> host((size_t)n_seq * L * 2);
-    for (int q = 0; q < n_seq; q++)
+    for (int q = 0; q < n_seq; q++) {
+        const ps_hip_model::seq_state &s = q < have ? m->seqs[q] : add[q - have];
         for (size_t i = 0; i < L; i++) {
-            const bool parked = q < have && q != m->cur_seq;
-            host[((size_t)q * L + i) * 2]     = q >= have ? add[q - have].k_cache[i] : (parked ? m->seqs[q].k_cache[i] : m->k_cache[i]);
-            host[((size_t)q * L + i) * 2 + 1] = q >= have ? add[q - have].v_cache[i] : (parked ? m->seqs[q].v_cache[i] : m->v_cache[i]);
+            host[((size_t)q * L + i) * 2]     = s.k_cache[i];
+            host[((size_t)q * L + i) * 2 + 1] = s.v_cache[i];
         }
-    if (hipMemcpyAsync(kv, host.data(), host.size() * sizeof(float *), hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    }
+    if (hipMemcpyAsync(kv, host.data(), host.size() * sizeof(float *), hipMemcpyHostToDevice, c->stream) != hipSuccess || sync_stream(m) != hipSuccess) {
         (void)hipGetLastError();
         return fail();
     }
@@ -923,7 +925,6 @@ static int seq_grow(ps_hip_model *m, int n_seq) {
     }
     for (void *p : fresh) m->owned.push_back(p);
     m->seq_kv_dev = kv; m->seq_tab = tab; m->seq_ids_dev = ids;
-    if (m->seqs.empty()) m->seqs.resize(1);
     for (auto &q : add) m->seqs.push_back(std::move(q));
     return 0;
 }
@@ -931,7 +932,7 @@ int ps_hip_model_seq_reserve(ps_hip_model *m, int n_seq) {
     ps_hip_ctx *c = m->ctx;
     if (int rc = settle_pending(m)) return rc;
     if (n_seq < 1) PS_FAIL(c, "seq_reserve: at least one sequence");
-    if (n_seq < ps_hip_model_seq_count(m)) PS_FAIL(c, "seq_reserve: the model holds more sequences already (growing only)");
+    if (n_seq < (int)m->seqs.size()) PS_FAIL(c, "seq_reserve: the model holds more sequences already (growing only)");
     if (n_seq > 1 && (m->mode & 8)) PS_FAIL(c, "seq_reserve: the fp16-KV decode mode (mode bit 3) mirrors one cache; it does not combine with sequences");
     return seq_grow(m, n_seq);
 }
@@ -940,14 +941,8 @@ int ps_hip_model_seq_reserve(ps_hip_model *m, int n_seq) {
 int ps_hip_model_seq_select(ps_hip_model *m, int s) {
     ps_hip_ctx *c = m->ctx;
     if (int rc = settle_pending(m)) return rc;
-    if (s < 0 || s >= ps_hip_model_seq_count(m)) PS_FAIL(c, "seq_select: no such sequence");
+    if (s < 0 || s >= (int)m->seqs.size()) PS_FAIL(c, "seq_select: no such sequence");
     if (s == m->cur_seq) return 0;
-    auto &old = m->seqs[m->cur_seq];
-    old.k_cache.swap(m->k_cache); old.v_cache.swap(m->v_cache); old.kv_vis_host.swap(m->kv_vis_host);
-    old.kv_vis_dev = m->kv_vis_dev; old.n_hidden = m->n_hidden; old.position = m->position;
-    auto &nw = m->seqs[s];
-    m->k_cache.swap(nw.k_cache); m->v_cache.swap(nw.v_cache); m->kv_vis_host.swap(nw.kv_vis_host);
-    m->kv_vis_dev = nw.kv_vis_dev; m->n_hidden = nw.n_hidden; m->position = nw.position;
     m->cur_seq = s;
     m->pin_argmax_n = 0;
     drop_graphs(m);
@@ -964,24 +959,23 @@ static int batch_check(ps_hip_model *m, const int32_t *seq_ids, const int32_t *t
     if (!seq_ids || !tokens) PS_FAIL(c, w + "null argument");
     for (int i = 0; i < n; i++) {
         const int s = seq_ids[i];
-        if (s < 0 || s >= ps_hip_model_seq_count(m)) PS_FAIL(c, w + "no such sequence: " + std::to_string(s));
+        if (s < 0 || s >= (int)m->seqs.size()) PS_FAIL(c, w + "no such sequence: " + std::to_string(s));
         for (int j = 0; j < i; j++) if (seq_ids[j] == s) PS_FAIL(c, w + "sequence " + std::to_string(s) + " appears twice in one step");
-        if (seq_hidden(m, s)) PS_FAIL(c, w + "sequence " + std::to_string(s) + " has hidden KV slots (kv_mask); unmask first");
-        if (ps_hip_model_seq_position(m, s) + (size_t)steps > m->cfg.seq_len) PS_FAIL(c, w + "KV cache of sequence " + std::to_string(s) + " is full (n_ctx)");
-        if (tokens[i] < 0 || (uint32_t)tokens[i] >= m->cfg.vocab_size) PS_FAIL(c, w + "token id out of range");
+        if (m->seqs[s].n_hidden) PS_FAIL(c, w + "sequence " + std::to_string(s) + " has hidden KV slots (kv_mask); unmask first");
+        if (m->seqs[s].position + (size_t)steps > m->cfg.seq_len) PS_FAIL(c, w + "KV cache of sequence " + std::to_string(s) + " is full (n_ctx)");
     }
-    return 0;
+    return check_tokens(m, tokens, n, who);
 }
 // tables and tokens to the device; the stream is idle afterwards
 static int batch_begin(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, psl_seqs_args *sq) {
     ps_hip_ctx *c = m->ctx;
-    if (int rc = seq_grow(m, 1)) return rc; // (a model that never reserved: its one sequence, and the tables)
+    if (int rc = seq_grow(m, 1)) return rc; // (a model that never reserved: the device tables of its one sequence)
     PS_CHECK(c, hipSetDevice(c->device));
     ps_seq_table t{};
     int64_t rows = 0;
     int top = 0;
     for (int i = 0; i < n; i++) {
-        const int pos = (int)ps_hip_model_seq_position(m, seq_ids[i]);
+        const int pos = (int)m->seqs[seq_ids[i]].position;
         t.col[i].seq = seq_ids[i]; t.col[i].pos = pos;
         rows += pos + 1;
         if (pos + 1 > top) top = pos + 1;
@@ -989,18 +983,14 @@ static int batch_begin(ps_hip_model *m, const int32_t *seq_ids, const int32_t *t
     m->pin_argmax_n = 0;
     PS_CHECK(c, hipMemcpyAsync(m->seq_tab, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
     PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    PS_CHECK(c, hipStreamSynchronize(c->stream)); // (both sources are host temporaries)
-    m->pin_busy = false; m->pin_argmax_pending = false;
+    PS_CHECK(c, sync_stream(m)); // (both sources are host temporaries)
     sq->tab = m->seq_tab; sq->kv = m->seq_kv_dev; sq->n_layers = (int)m->cfg.n_layers; sq->layer = 0; sq->n_kv_max = top;
     // the rows this step reads, K and V of every layer: read once per step, so non-temporal where they cannot stay in the memory-side cache anyway (as enqueue_forward's rule)
     sq->kv_stream = g_kv_stream_force >= 0 ? g_kv_stream_force : ((int64_t)m->cfg.n_layers * 2 * rows * m->cfg.kv_dim * 4 > ((int64_t)160 << 20) ? 1 : 0);
     return 0;
 }
 static void batch_advance(ps_hip_model *m, const int32_t *seq_ids, int n, size_t by) {
-    for (int i = 0; i < n; i++) {
-        if (seq_ids[i] == m->cur_seq) m->position += by;
-        else m->seqs[seq_ids[i]].position += by;
-    }
+    for (int i = 0; i < n; i++) m->seqs[seq_ids[i]].position += by;
 }
 int ps_hip_model_decode_batch(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int lm_head, int32_t *argmax_host) {
     ps_hip_ctx *c = m->ctx;
@@ -1008,9 +998,11 @@ int ps_hip_model_decode_batch(ps_hip_model *m, const int32_t *seq_ids, const int
     if (int rc = batch_check(m, seq_ids, tokens, n, 1, "decode_batch")) return rc;
     psl_seqs_args sq{};
     if (int rc = batch_begin(m, seq_ids, tokens, n, &sq)) return rc;
-    if (int rc = enqueue_forward(m, n, lm_head != 0, false, false, false, false, &sq)) return rc;
+    fwd_opts o;
+    o.lm_head = lm_head != 0; o.sq = &sq;
+    if (int rc = enqueue_forward(m, n, o)) return rc;
     if (lm_head && argmax_host) PS_CHECK(c, hipMemcpyAsync(argmax_host, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
+    PS_CHECK(c, sync_stream(m));
     batch_advance(m, seq_ids, n, 1);
     return 0;
 }
@@ -1026,12 +1018,14 @@ int ps_hip_model_decode_batch_greedy(ps_hip_model *m, const int32_t *seq_ids, co
     psl_seqs_args sq{};
     if (int rc = batch_begin(m, seq_ids, tokens, n, &sq)) return rc;
     const int top0 = sq.n_kv_max;
+    fwd_opts o;
+    o.lm_head = true; o.advance = true; o.sq = &sq;
     for (int s = 0; s < steps; s++) {
         sq.n_kv_max = top0 + s;
-        if (int rc = enqueue_forward(m, n, true, false, true, false, false, &sq)) { (void)hipStreamSynchronize(c->stream); return rc; }
+        if (int rc = enqueue_forward(m, n, o)) { (void)sync_stream(m); return rc; }
     }
     PS_CHECK(c, hipMemcpyAsync(out_ids, m->seq_ids_dev, (size_t)steps * n * 4, hipMemcpyDeviceToHost, c->stream));
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
+    PS_CHECK(c, sync_stream(m));
     batch_advance(m, seq_ids, n, (size_t)steps);
     return 0;
 }
@@ -1042,13 +1036,12 @@ int ps_hip_model_argmax(ps_hip_model *m, int n, int32_t *ids_host) {
     if (n <= 0 || n > m->max_batch) PS_FAIL(c, "model_argmax: batch size out of range");
     if (int rc = settle_pending(m)) return rc;
     if (m->pin_argmax_n >= n) { // the last forward was a lowered one and left its ids in pinned memory
-        if (m->pin_argmax_pending) { PS_CHECK(c, hipStreamSynchronize(c->stream)); m->pin_busy = false; m->pin_argmax_pending = false; }
+        if (m->pin_argmax_pending) PS_CHECK(c, sync_stream(m));
         memcpy(ids_host, m->pin_argmax, (size_t)n * 4);
         return 0;
     }
     PS_CHECK(c, hipMemcpyAsync(ids_host, m->argmax_dev, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    PS_CHECK(c, hipStreamSynchronize(c->stream));
-    m->pin_busy = false; m->pin_argmax_pending = false;
+    PS_CHECK(c, sync_stream(m));
     return 0;
 }
 const float *ps_hip_model_scratch(const ps_hip_model *m, int which) {
@@ -1061,8 +1054,8 @@ const float *ps_hip_model_scratch(const ps_hip_model *m, int which) {
     }
     return nullptr;
 }
-const float *ps_hip_model_k_cache(const ps_hip_model *m, int L) { return m->k_cache[L]; }
-const float *ps_hip_model_v_cache(const ps_hip_model *m, int L) { return m->v_cache[L]; }
+const float *ps_hip_model_k_cache(const ps_hip_model *m, int L) { return m->cur().k_cache[L]; }
+const float *ps_hip_model_v_cache(const ps_hip_model *m, int L) { return m->cur().v_cache[L]; }
 uint64_t ps_hip_model_weight_bytes_per_token(const ps_hip_model *m) { return m->weight_bytes; }
 // Roofline helper for bench.py: replay mat-vec launches of one single-token forward exactly as the decode step issues
 // them (same kernels, same fused prologues; every layer's own weights -> the stream is HBM-cold like a real step),
@@ -1077,7 +1070,7 @@ int ps_hip_model_bench_matmul(ps_hip_model *m, int reps, int which, int bs, doub
     ps_hip_ctx *c = m->ctx;
     if (bs < 1 || bs > m->max_batch) PS_FAIL(c, "bench_matmul: batch size out of range");
     const ps_llm_config &f = m->cfg;
-    const int64_t dim = f.dim, kvd = f.kv_dim, hid = f.hidden_dim;
+    const int64_t dim = f.dim, hid = f.hidden_dim;
     hipEvent_t e0, e1;
     PS_CHECK(c, hipEventCreate(&e0));
     PS_CHECK(c, hipEventCreate(&e1));
@@ -1087,41 +1080,31 @@ int ps_hip_model_bench_matmul(ps_hip_model *m, int reps, int which, int bs, doub
         const bool qkv = which == 0 || which == 2, op = which == 0 || which == 3, gu = which == 0 || which == 1, dn = which == 0 || which == 4;
         for (uint32_t L = 0; L < f.n_layers; L++) {
             if (qkv) {
-                psk_gemv_args g{};
-                g.n_w = 3; g.w[0] = m->wq[L]; g.w[1] = m->wk[L]; g.w[2] = m->wv[L];
-                g.out[0] = m->q; g.out[1] = m->k; g.out[2] = m->v; g.ldo[0] = dim; g.ldo[1] = kvd; g.ldo[2] = kvd;
-                if (m->qwen2) { g.bias[0] = m->bq[L]; g.bias[1] = m->bk[L]; g.bias[2] = m->bv[L]; }
-                g.pro = 1; g.pro_x = m->x; g.pro_norm_w = m->attn_norm[L]; g.pro_eps = f.norm_eps;
-                if (mm(m, g, a1, dim, bs)) return 2;
+                if (mm(m, mm_args(m, MM_QKV, L), a1, dim, bs)) return 2;
                 if (count) launches += 1;
             }
             if (op) {
-                psk_gemv_args go{};
-                go.n_w = 1; go.w[0] = m->wo[L]; go.out[0] = m->hb; go.ldo[0] = dim; // (not into x: the replay must not drift)
-                go.pro = 2; go.pro_x = m->att;
+                psk_gemv_args go = mm_args(m, MM_O, L);
+                go.out[0] = m->hb; go.residual = nullptr; // (not into x: the replay must not drift)
                 if (mm(m, go, a1, dim, bs)) return 2;
                 if (count) launches += 1;
             }
             if (gu) {
-                psk_gemv_args gf{};
-                gf.n_w = 2; gf.w[0] = m->wg[L]; gf.w[1] = m->wu[L]; gf.out[0] = m->g1; gf.out[1] = m->g1; gf.ldo[0] = hid; gf.ldo[1] = hid; gf.silu_pair = 1;
-                gf.pro = 1; gf.pro_x = m->x; gf.pro_norm_w = m->ffn_norm[L]; gf.pro_eps = f.norm_eps;
+                psk_gemv_args gf = mm_args(m, MM_GATE_UP, L);
+                gf.out[0] = m->g1; gf.out[1] = m->g1; // (hb is the O replay's output)
                 if (mm(m, gf, a1, dim, bs)) return 2;
                 if (count) launches += 1;
             }
             if (dn) {
-                psk_gemv_args gd{};
-                gd.n_w = 1; gd.w[0] = m->wd[L]; gd.out[0] = m->att; gd.ldo[0] = dim;
-                gd.pro = 2; gd.pro_x = m->g1;
+                psk_gemv_args gd = mm_args(m, MM_DOWN, L);
+                gd.out[0] = m->att; gd.residual = nullptr; // (no residual either: x stays what it was)
+                gd.pro = 2; gd.pro_x = m->g1;              // (always the prologue quantizer, on the gate/up replay's output)
                 if (mm(m, gd, a2, hid, bs)) return 2;
                 if (count) launches += 1;
             }
         }
         if (which == 0 || which == 5) {
-            psk_gemv_args gl{};
-            gl.n_w = 1; gl.w[0] = m->output ? m->output : m->token_embd; gl.out[0] = m->logits; gl.ldo[0] = f.vocab_size;
-            gl.pro = 1; gl.pro_x = m->x; gl.pro_norm_w = m->output_norm; gl.pro_eps = f.norm_eps;
-            if (mm(m, gl, a1, dim, bs)) return 2;
+            if (mm(m, mm_args(m, MM_LM_HEAD, 0), a1, dim, bs)) return 2;
             if (count) launches += 1;
         }
         return 0;
@@ -1146,18 +1129,13 @@ int ps_hip_model_bench_matmul(ps_hip_model *m, int reps, int which, int bs, doub
     return 0;
 }
 
-// PS_HIP_MODE_OR: mode bits OR-ed into every model's mode (A/B runs of unmodified drivers, e.g. bench.py with 16 = two-launch attention)
-static int mode_env_or() {
-    static const int v = [] { const char *e = getenv("PS_HIP_MODE_OR"); return e ? atoi(e) : 0; }();
-    return v;
-}
 int ps_hip_model_set_mode(ps_hip_model *m, int mode) {
     mode |= mode_env_or();
     if (mode & 64) { m->attn1_disabled = false; mode &= ~64; } // explicit re-arm of the one-launch attention after a time-out
     if (m->attn1_disabled) mode |= 16;                         // sticky: a later set_mode without bit 4 does not bring the form that timed out back
     if ((mode & 8) && m->seqs.size() > 1) { m->ctx->err = "set_mode: the fp16-KV decode mode mirrors one cache; it does not combine with sequences (seq_reserve)"; return 2; }
     if ((mode & 8) && m->k16.empty()) { // fp16 mirrors of the caches: filled from now on, so the cache must be empty
-        if (m->position != 0) { m->ctx->err = "set_mode: the fp16-KV decode mode must be switched on while the cache is empty"; return 2; }
+        if (m->cur().position != 0) { m->ctx->err = "set_mode: the fp16-KV decode mode must be switched on while the cache is empty"; return 2; }
         const size_t n = (size_t)m->cfg.seq_len * m->cfg.kv_dim * 2;
         m->k16.assign(m->cfg.n_layers, nullptr); m->v16.assign(m->cfg.n_layers, nullptr);
         for (uint32_t i = 0; i < m->cfg.n_layers; i++) {
@@ -1167,7 +1145,7 @@ int ps_hip_model_set_mode(ps_hip_model *m, int mode) {
         }
         if (dmalloc(m, (void **)&m->attn_part, (size_t)m->cfg.n_heads * 32 * (m->cfg.head_size + 2) * 4)) return 2;
     }
-    if ((mode & 8) && !(m->mode & 8) && m->position != 0) { m->ctx->err = "set_mode: the fp16-KV decode mode must be switched on while the cache is empty"; return 2; }
+    if ((mode & 8) && !(m->mode & 8) && m->cur().position != 0) { m->ctx->err = "set_mode: the fp16-KV decode mode must be switched on while the cache is empty"; return 2; }
     if ((m->mode ^ mode) & (62 | 128)) drop_graphs(m); // the captured steps bake the launch plan in
     m->mode = mode;
     return 0;
