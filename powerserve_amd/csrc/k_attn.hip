@@ -19,6 +19,7 @@
 #include "ps_expf.h"
 #include "ps_ops.h"
 #include "ps_quant_dev.h"
+#include "ps_attn1_dev.h"
 
 namespace {
 
@@ -124,7 +125,6 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(psl_attn_args a) {
 // pairs), and GGML_F32x8_REDUCE becomes 31 element-wise adds of tiles in its own association.  No cross-lane reduction
 // at all; a K row is fetched once per 16 positions and meets every column of the batch.
 // grid (ceil(n_ctx / 64), n_kv_heads, SCM_Z): one wave per 16 positions, the column tiles split over blockIdx.z.
-typedef float ps_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int SCM_Z = 8;
 // Operands go through LDS: a lane's operand run is 128 B of one row, and fetched directly a wave instruction touches 64
 // cache lines for 1 KiB (the CU's address unit, not the matrix core, set the time).  So a wave fetches its 16 K rows with
@@ -564,6 +564,8 @@ __global__ __launch_bounds__(NT) void attn_decode2_kernel(psl_attn_args a) {
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 if (g < r2) { // (uniform)
+                    // (a1_score of ps_attn1_dev.h, kept as text here: called instead, the <*, 1024, *> instantiations of this kernel compile to three more s_waitcnt each,
+                    //  with or without __restrict__ on q; every other figure and qkv_attn_kernel, which calls it, are unchanged -- HISTORY.md, round 9)
                     float x[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int m = 0; m < NV; m++) {
@@ -610,16 +612,7 @@ __global__ __launch_bounds__(NT) void attn_decode2_kernel(psl_attn_args a) {
     __syncthreads();
     mark(4);
     if (wave == 0) { // (uniform) the polling wave asks for its V rows AFTER the poll: loads return in order
-        if (tid == 0) {
-            unsigned *ctr = a.tick + kvh * 64; // (a 256-byte stretch per kv head)
-            const unsigned ticket = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned target = (ticket / (unsigned)G + 1u) * (unsigned)G; // exactly G arrivals per head and launch
-            int spins = 0;
-            while ((int)(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1 << 16)) { __hip_atomic_store(a.sync + 31, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; } // never hang the GPU: the host turns the flag into an error
-            }
-        }
+        if (tid == 0) a1_rendezvous<true>(a.tick + kvh * 64, 0u, (unsigned)G, a.sync + 31); // (a 256-byte stretch per kv head; time-out: the host turns the flag into an error)
         asm volatile("" ::: "memory"); // (nothing below moves above the poll)
     }
     __syncthreads();
@@ -696,9 +689,7 @@ __global__ __launch_bounds__(NT) void attn_decode2_kernel(psl_attn_args a) {
         const int j0 = (t + LPH * k) * 8;
         if (!hl) continue;
         if (j0 + 8 <= n8) {
-            ps_v_expf_n<8>(sv[k], mx);
-            const float a0 = __fadd_rn(sv[k][4], sv[k][0]), a1 = __fadd_rn(sv[k][5], sv[k][1]), a2 = __fadd_rn(sv[k][6], sv[k][2]), a3 = __fadd_rn(sv[k][7], sv[k][3]);
-            rs += (double)__fadd_rn(__fadd_rn(a0, a2), __fadd_rn(a1, a3));
+            rs += (double)a1_exp8(sv[k], mx);
             if (j0 + 8 <= np) {
                 *(float4 *)(pl + g * RS + j0)     = make_float4(sv[k][0], sv[k][1], sv[k][2], sv[k][3]);
                 *(float4 *)(pl + g * RS + j0 + 4) = make_float4(sv[k][4], sv[k][5], sv[k][6], sv[k][7]);
@@ -752,9 +743,7 @@ __global__ __launch_bounds__(NT) void attn_decode2_kernel(psl_attn_args a) {
         auto chain = [&](const float (&av)[4], const float (&bv)[4], int s0) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float p = __fmul_rn(bv[i], inv); // p_j = e_j * (float)(1/sum)
-                const float b = __uint_as_float(__float_as_uint(p) & ((bl && s0 + i < n_it) ? 0xffffffffu : 0u)); // (a mask, not a branch)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], b, acc, 0, 0, 0); // sum = x*y + sum, x = V row (src0)
+                acc = a1_pv_step(acc, av[i], bv[i], inv, bl && s0 + i < n_it); // p_j = e_j * (float)(1/sum)
             }
         };
         if (n_it > 0) {

@@ -14,11 +14,6 @@
 //     28 units = half a row group).
 // Epilogues: EPI 0 bias / residual, EPI 1 SiLU(gate)*up, EPI 2 RoPE + KV-cache append (QKV).
 #include "ps_g4_dev.h"
-#ifndef G4_OUT_WT
-#define G4_OUT_WT 1 // (round 6) the result rows are stored write-through: nothing dirty is left for the end-of-kernel write-back, the next launch finds the row in memory; same-box A/B,
-                    // three rounds (profiles/r06_out_wt_ab.txt): all mat-vecs of a token 1.239 -> 1.226 ms, 8B decode 596.3 -> 599.7 tok/s
-#endif
-namespace { __device__ __forceinline__ void g4_out(float *p, const float v) { if (G4_OUT_WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v; } }
 
 namespace {
 constexpr int G4_PAIR = 0; // units of a chunk the scheduler may interleave (0: one at a time)
@@ -202,10 +197,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
                     if (wave + i * NW < n_pairs) { // (wave-uniform)
 #pragma unroll
                         for (int h = 0; h < 2; h++) {
-                            ss += (double)__fmul_rn(xv[i][h].x, xv[i][h].x);
-                            ss += (double)__fmul_rn(xv[i][h].y, xv[i][h].y);
-                            ss += (double)__fmul_rn(xv[i][h].z, xv[i][h].z);
-                            ss += (double)__fmul_rn(xv[i][h].w, xv[i][h].w);
+                            ch_sumsq4(ss, xv[i][h]);
                         }
                     }
                 }
@@ -215,11 +207,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
                 __syncthreads();
                 pmark(25);
                 if (STAGED && XW == 1 && DC > 1) issue(q[1], h[1], tS[1], uS[1]); // (XW 2, 3: after the quantizer instead, with the others)
-                double tot_ss = 0.0;
-#pragma unroll
-                for (int i = 0; i <= NW; i++) tot_ss += red[i];
-                const float mean = (float)(tot_ss / (double)K);
-                scale            = __fdiv_rn(1.0f, sqrtf(__fadd_rn(mean, p.eps)));
+                scale = ch_rms_scale<NW>(red, K, p.eps);
                 pmark(26);
             }
 #pragma unroll
@@ -230,7 +218,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
                 if (PRO == 1) {
                     const float w8[8] = {wv[i][0].x, wv[i][0].y, wv[i][0].z, wv[i][0].w, wv[i][1].x, wv[i][1].y, wv[i][1].z, wv[i][1].w};
 #pragma unroll
-                    for (int k = 0; k < 8; k++) v[k] = __fmul_rn(v[k], __fmul_rn(w8[k], scale));
+                    for (int k = 0; k < 8; k++) v[k] = ch_norm(v[k], w8[k], scale);
                 }
                 g4_quantize_pair(v, tp * 512 + lane * 8, tp, lq, ld, lb, live);
             }
@@ -355,21 +343,19 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
                         const int e = (int)(row % R.head_size);
                         float res = v;
                         if (e < R.n_dims) {
-                            const float c = ea, sn = eb;
-                            const float x0 = (e & 1) ? vp : v, x1 = (e & 1) ? v : vp;
-                            res = ps_rope_one(x0, x1, c, sn, (e & 1) != 0);
+                            res = ch_rope(v, vp, e, ea, eb);
                         }
                         if (role == 0) o[row] = res; else { R.k_cache[(int64_t)kv_pos * R.kv_dim + row] = res; if (R.k16) R.k16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)res; }
                     }
                 }
             } else if (u == 0 && row < Nw) {
                 if (EPI == 1) {
-                    g4_out(o + row, g4_silu_mul(ygate, y, exp_tab));
+                    ps_out_wt(o + row, g4_silu_mul(ygate, y, exp_tab));
                 } else {
                     float v = y;
                     if (b) v = __fadd_rn(v, ec);
                     if (p.residual && wi == 0) v = __fadd_rn(ea, v);
-                    g4_out(o + row, v);
+                    ps_out_wt(o + row, v);
                 }
             }
             acc0 = 0.f; acc1 = 0.f; accm = 0.f;

@@ -27,12 +27,6 @@ template <int WT> struct GBT;
 template <> struct GBT<PS_Q4_0> { static constexpr int RG = 16, LPR = 4, RECF = 3; }; // rows per group, lanes per row, float4s per record
 template <> struct GBT<PS_Q8_0> { static constexpr int RG = 8, LPR = 8, RECF = 2; };
 
-__device__ __forceinline__ float gb_silu_mul(float g, float u, const uint64_t *tab) { // src/backend/ggml/ggml.cpp:115-129, expf table in LDS
-    float val = g;
-    val       = __fmul_rn(val, __fdiv_rn(1.0f, __fadd_rn(1.0f, ps_expf_glibc(-val, tab))));
-    return __fmul_rn(val, u);
-}
-
 struct GBMat {
     const uint8_t *qs, *aux;
     float *out;
@@ -195,29 +189,22 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvb_kernel(const GBParams p) 
                 double ss = 0.0;
 #pragma unroll
                 for (int i = 0; i < TPW; i++) {
-                    ss += (double)__fmul_rn(xv[i].x, xv[i].x);
-                    ss += (double)__fmul_rn(xv[i].y, xv[i].y);
-                    ss += (double)__fmul_rn(xv[i].z, xv[i].z);
-                    ss += (double)__fmul_rn(xv[i].w, xv[i].w);
+                    ch_sumsq4(ss, xv[i]);
                 }
                 ss = wave_sum_d_dpp(ss);
                 if (lane == 0) red[wave] = ss;
                 __syncthreads();
-                double tot_ss = 0.0;
-#pragma unroll
-                for (int i = 0; i <= NW; i++) tot_ss += red[i];
-                const float mean = (float)(tot_ss / (double)K);
-                scale            = __fdiv_rn(1.0f, sqrtf(__fadd_rn(mean, p.eps)));
+                scale = ch_rms_scale<NW>(red, K, p.eps);
             }
 #pragma unroll
             for (int i = 0; i < TPW; i++) {
                 const int e = (wave + i * NW) * 256 + lane * 4;
                 float v[4] = {xv[i].x, xv[i].y, xv[i].z, xv[i].w}; // (zeros past the row's end)
                 if (PRO == 1) {
-                    v[0] = __fmul_rn(v[0], __fmul_rn(wv[i].x, scale));
-                    v[1] = __fmul_rn(v[1], __fmul_rn(wv[i].y, scale));
-                    v[2] = __fmul_rn(v[2], __fmul_rn(wv[i].z, scale));
-                    v[3] = __fmul_rn(v[3], __fmul_rn(wv[i].w, scale));
+                    v[0] = ch_norm(v[0], wv[i].x, scale);
+                    v[1] = ch_norm(v[1], wv[i].y, scale);
+                    v[2] = ch_norm(v[2], wv[i].z, scale);
+                    v[3] = ch_norm(v[3], wv[i].w, scale);
                 }
                 gb_quantize<WT>(v, e, e < K, lq, ld);
             }
@@ -306,16 +293,14 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvb_kernel(const GBParams p) 
                         const int e = (int)(row % R.head_size);
                         float res = v;
                         if (e < R.n_dims) {
-                            const float c = ea, sn = eb;
-                            const float x0 = (e & 1) ? vp : v, x1 = (e & 1) ? v : vp;
-                            res = ps_rope_one(x0, x1, c, sn, (e & 1) != 0);
+                            res = ch_rope(v, vp, e, ea, eb);
                         }
                         if (wi == 0) o[row] = res; else { R.k_cache[(int64_t)kv_pos * R.kv_dim + row] = res; if (R.k16) R.k16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)res; }
                     }
                 }
             } else if (u == 0 && row < Nw) {
                 if (EPI == 1) {
-                    ps_out_wt(o + row, gb_silu_mul(ygate, y, exp_tab));
+                    ps_out_wt(o + row, g4_silu_mul(ygate, y, exp_tab));
                 } else {
                     float v = y;
                     if (b) v = __fadd_rn(v, ec);

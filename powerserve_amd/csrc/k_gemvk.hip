@@ -232,21 +232,14 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
                     if (tp < n_pairs && (int64_t)tp * 512 + lane * 8 < K) { // (lanes of a tile that does not exist add nothing)
 #pragma unroll
                         for (int h = 0; h < 2; h++) {
-                            ss += (double)__fmul_rn(xv[i][h].x, xv[i][h].x);
-                            ss += (double)__fmul_rn(xv[i][h].y, xv[i][h].y);
-                            ss += (double)__fmul_rn(xv[i][h].z, xv[i][h].z);
-                            ss += (double)__fmul_rn(xv[i][h].w, xv[i][h].w);
+                            ch_sumsq4(ss, xv[i][h]);
                         }
                     }
                 }
                 ss = wave_sum_d_dpp(ss);
                 if (lane == 0) red[wave] = ss;
                 __syncthreads();
-                double tot_ss = 0.0;
-#pragma unroll
-                for (int i = 0; i <= NW; i++) tot_ss += red[i];
-                const float mean = (float)(tot_ss / (double)K);
-                scale            = __fdiv_rn(1.0f, sqrtf(__fadd_rn(mean, p.eps)));
+                scale = ch_rms_scale<NW>(red, K, p.eps);
             }
 #pragma unroll
             for (int i = 0; i < PPW; i++) {
@@ -256,7 +249,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
                 if (PRO == 1) {
                     const float w8[8] = {wv[i][0].x, wv[i][0].y, wv[i][0].z, wv[i][0].w, wv[i][1].x, wv[i][1].y, wv[i][1].z, wv[i][1].w};
 #pragma unroll
-                    for (int k = 0; k < 8; k++) v[k] = __fmul_rn(v[k], __fmul_rn(w8[k], scale));
+                    for (int k = 0; k < 8; k++) v[k] = ch_norm(v[k], w8[k], scale);
                 }
                 g4_quantize_pair(v, tp * 512 + lane * 8, tp, lq, ld, lb, live, n_units);
             }
@@ -346,9 +339,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
                         const int e = (int)(row % R.head_size);
                         float res = v;
                         if (e < R.n_dims) {
-                            const float c = ea, sn = eb;
-                            const float x0 = (e & 1) ? vp : v, x1 = (e & 1) ? v : vp;
-                            res = ps_rope_one(x0, x1, c, sn, (e & 1) != 0);
+                            res = ch_rope(v, vp, e, ea, eb);
                         }
                         if (role == 0) o[row] = res; else { R.k_cache[(int64_t)kv_pos * R.kv_dim + row] = res; if (R.k16) R.k16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)res; }
                     }

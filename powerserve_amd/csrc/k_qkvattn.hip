@@ -1,7 +1,8 @@
 // One launch for the head of a decode layer (round 6): the Q / K / V mat-vec (RMSNorm + Q8_K quantizer prologue, RoPE + KV-append epilogue: gemv4_kernel<8, 2, 2, 2, 2, 1>
 // of k_gemv4.hip) AND the single-token attention (attn_decode2_kernel<NV, 512> of k_attn.hip), four launches per layer instead of five.
 // Reference: src/model/module/norm_attention.cpp:62-147 (RMS_NORM, three MAT_MULs, ROPE x 2, the KV append, K.q, SOFTMAX_EXT, V.p, PERMUTE + CONT); the arithmetic
-// of both halves is the unfused kernels', statement by statement, so the bits are theirs.
+// of both halves is the unfused kernels': the statements that round are shared functions (ps_gemv_dev.h: ch_sumsq4 / ch_rms_scale / ch_norm, g4_quantize_pair, g4_unit, row_reduce,
+// ch_rope; ps_attn1_dev.h: a1_score, a1_exp8, a1_pv_step, a1_rendezvous), the loops and addresses around them are this kernel's own copy (HISTORY.md round 9 says why).
 //
 // Why this edge and no other: Q / K / V -> attention is the only edge of a layer that is NOT an all-to-all.  A kv head's attention needs that head group's rows only
 // (r2 q heads + k + v = (r2 + 2) * head_size rows), the one-launch attention already gives a kv head head_size / 4 workgroups (4 V channels each) that meet at a
@@ -25,13 +26,13 @@
 #include "ps_expf.h"
 #include "ps_g4_dev.h"
 #include "ps_ops.h"
+#include "ps_attn1_dev.h"
 // KVS (psl_attn_args::kv_stream, round 6): the cached K rows and V channels are read with NON-TEMPORAL loads, and the wave that owns the new position then asks for the new row
 // only, not for its seven streamed neighbours again.  They are read once per token; when the model's whole cache is larger than the memory-side cache (8B at n_kv 2048: 537 MB)
 // nothing of it survives to the next token and, read with plain loads, it displaces everything else there and in the L2s: same-box A/B, 8B decode over 32 steps
 // (profiles/r06_kv_nt_ab.txt): 577.5 tok/s plain, K 584.6, V 582.6, both 587.1, with the new-row request 589.8 (+2.1 %).  A cache that fits stays there: plain loads (k_attn.hip).
 
 namespace {
-typedef float ps_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void qa_store_f(float *p, float v) { __hip_atomic_store((uint32_t *)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 struct QAParams {
@@ -47,20 +48,6 @@ struct QAParams {
 };
 
 constexpr int QA_MAXCTX = 4096, QA_THREADS = 9 * 64;
-
-// One bounded rendezvous of the G workgroups of a kv head on a counter that is never reset (attn_decode2's exchange, epoch = count / G).  `base` is the counter as this
-// workgroup read it at kernel ENTRY: every earlier launch is complete (a multiple of G) and of this launch fewer than G workgroups can have arrived before this one
-// has, so base / G IS this launch's epoch whatever the timing -- the arrival itself is then an atomic add nobody waits for (a returned ticket is a memory round
-// trip on the critical path: 2.0 us from "rows stored" to "rendezvous complete" in profiles/r06_fused_timeline_v1.txt).
-__device__ __forceinline__ void qa_rendezvous(unsigned *ctr, const unsigned base, const unsigned G, unsigned *flag) {
-    (void)__hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned target = (base / G + 1u) * G;
-    int spins = 0;
-    while ((int)(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > (1 << 16)) { __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; } // never hang the GPU: the host turns the flag into a re-run on the unfused launches
-    }
-}
 
 // Rendezvous A as tagged granules (round 7).  What a workgroup needs from the others before its scores is small -- r2 q rows, the new K row and its four
 // channels of the new V column: (r2 + 1) * head_size + 4 floats, 2.6 KB for 8B -- so the data IS the flag (MI355X_MICROARCH.md, handoff-1to1 vs handoff-flag):
@@ -126,7 +113,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
     const float *vbase = a.v_cache + ((int64_t)kvh * hs + bx * 4) * a.n_ctx;
     int pos0 = 0;
     float4 kf[PASSES][NV]; // waves 0-7: K row of this lane's position in each pass
-    unsigned baseA = 0, baseB = 0; // the rendezvous counters as they stood at entry (wave 8, lane 0: qa_rendezvous)
+    unsigned baseA = 0, baseB = 0; // the rendezvous counters as they stood at entry (wave 8, lane 0: a1_rendezvous)
     // waves 0-7: zeros past the cache length in the V rows (with granules before rendezvous A: it takes nothing from it)
     auto v_zero_tail = [&]() {
         for (int col = ((pos0 + 4) & ~3) + 4 * tid; col < RS - 36; col += 4 * NT) {
@@ -192,21 +179,14 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
             if (wave + i * NW < n_pairs) {
 #pragma unroll
                 for (int hh = 0; hh < 2; hh++) {
-                    ss += (double)__fmul_rn(xv[i][hh].x, xv[i][hh].x);
-                    ss += (double)__fmul_rn(xv[i][hh].y, xv[i][hh].y);
-                    ss += (double)__fmul_rn(xv[i][hh].z, xv[i][hh].z);
-                    ss += (double)__fmul_rn(xv[i][hh].w, xv[i][hh].w);
+                    ch_sumsq4(ss, xv[i][hh]);
                 }
             }
         }
         ss = wave_sum_d_dpp(ss);
         if (lane == 0) red_ss[wave] = ss;
         __syncthreads(); // #1
-        double tot_ss = 0.0;
-#pragma unroll
-        for (int i = 0; i <= NW; i++) tot_ss += red_ss[i];
-        const float mean  = (float)(tot_ss / (double)K);
-        const float scale = __fdiv_rn(1.0f, sqrtf(__fadd_rn(mean, p.eps)));
+        const float scale = ch_rms_scale<NW>(red_ss, K, p.eps);
 #pragma unroll
         for (int i = 0; i < PPW; i++) {
             const int tp = wave + i * NW;
@@ -214,7 +194,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
             float v[8] = {xv[i][0].x, xv[i][0].y, xv[i][0].z, xv[i][0].w, xv[i][1].x, xv[i][1].y, xv[i][1].z, xv[i][1].w};
             const float w8[8] = {wv[i][0].x, wv[i][0].y, wv[i][0].z, wv[i][0].w, wv[i][1].x, wv[i][1].y, wv[i][1].z, wv[i][1].w};
 #pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = __fmul_rn(v[k], __fmul_rn(w8[k], scale));
+            for (int k = 0; k < 8; k++) v[k] = ch_norm(v[k], w8[k], scale);
             g4_quantize_pair(v, tp * 512 + lane * 8, tp, lq, ld, lb, live);
         }
         mark(2); // activation quantized
@@ -324,8 +304,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
                     const int e = (int)(row % hs);
                     float res = v;
                     if (e < a.n_dims) {
-                        const float x0 = (e & 1) ? vp : v, x1 = (e & 1) ? v : vp;
-                        res = ps_rope_one(x0, x1, ea, eb, (e & 1) != 0);
+                        res = ch_rope(v, vp, e, ea, eb);
                     }
                     if (gran) qa_store_granule(gran + (wi == 0 ? (int)(row - (int64_t)kvh * r2 * hs) : r2 * hs + (int)(row - (int64_t)kvh * hs)), tagA, res);
                     if (wi == 0) qa_store_f(a.q + row, res); else qa_store_f(a.k_cache + (int64_t)kv_pos * kvd + row, res);
@@ -396,7 +375,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
                 }
                 if (__all(ok)) break;
                 __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1 << 16)) { if (lane == 0) __hip_atomic_store(a.sync + 31, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; } // (qa_rendezvous's budget and flag)
+                if (++spins > (1 << 16)) { if (lane == 0) __hip_atomic_store(a.sync + 31, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; } // (a1_rendezvous's budget and flag)
             }
             // into the LDS slots the attention reads: q -> qs, the K row -> sst (free until the scores), the V lines, then (later in this wave's LDS order) the new column over them
             if (lane < PS_EXP2F_N) etab[lane] = et;
@@ -413,7 +392,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
             // ---- rendezvous A: this workgroup's q / k / v are drained, then its ticket
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads(); // A0
-            if (lane == 0) qa_rendezvous(a.tick + kvh * 64 + 32, baseA, (unsigned)G, a.sync + 31);
+            if (lane == 0) a1_rendezvous<false>(a.tick + kvh * 64 + 32, baseA, (unsigned)G, a.sync + 31);
             asm volatile("" ::: "memory");
             mark(2); // rendezvous A complete
         }
@@ -470,22 +449,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
 #pragma unroll
                 for (int g = 0; g < 4; g++) {
                     if (g < r2) {
-                        float x[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int m = 0; m < NV; m++) {
-                            const float4 qv = *(const float4 *)(qs + g * hs + m * 32 + 4 * tq);
-                            x[0] = __fmaf_rn(kf[ps][m].x, qv.x, x[0]);
-                            x[1] = __fmaf_rn(kf[ps][m].y, qv.y, x[1]);
-                            x[2] = __fmaf_rn(kf[ps][m].z, qv.z, x[2]);
-                            x[3] = __fmaf_rn(kf[ps][m].w, qv.w, x[3]);
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; e++) x[e] = __fadd_rn(x[e], dpp_f<0x104>(x[e]));
-#pragma unroll
-                        for (int e = 0; e < 4; e++) x[e] = __fadd_rn(x[e], dpp_f<0x102>(x[e]));
-#pragma unroll
-                        for (int e = 0; e < 4; e++) x[e] = __fadd_rn(x[e], dpp_f<0x101>(x[e]));
-                        const float s = __fadd_rn(__fadd_rn(x[0], x[1]), __fadd_rn(x[2], x[3]));
+                        const float s = a1_score<NV>(kf[ps], qs + g * hs + 4 * tq);
                         if (tq == 0) sst[(((uw >> 2) + SPP * ps) * 4 + g) * 32 + (uw & 3) * 8 + p8] = s;
                     }
                 }
@@ -503,7 +467,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
     mark(8); // scores stored
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads(); // B3: every wave's score stores are drained
-    if (tid == NT) qa_rendezvous(a.tick + kvh * 64, baseB, (unsigned)G, a.sync + 31); // ---- rendezvous B (the scores of the kv head)
+    if (tid == NT) a1_rendezvous<false>(a.tick + kvh * 64, baseB, (unsigned)G, a.sync + 31); // ---- rendezvous B (the scores of the kv head)
     asm volatile("" ::: "memory");
     __syncthreads(); // B4
     mark(9);
@@ -571,9 +535,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
             const int j0 = (t + LPH * k) * 8;
             if (!hl) continue;
             if (j0 + 8 <= n8) {
-                ps_v_expf_n<8>(sv[k], mx);
-                const float a0 = __fadd_rn(sv[k][4], sv[k][0]), a1 = __fadd_rn(sv[k][5], sv[k][1]), a2 = __fadd_rn(sv[k][6], sv[k][2]), a3 = __fadd_rn(sv[k][7], sv[k][3]);
-                rs += (double)__fadd_rn(__fadd_rn(a0, a2), __fadd_rn(a1, a3));
+                rs += (double)a1_exp8(sv[k], mx);
                 if (j0 + 8 <= np) {
                     *(float4 *)(pl + g * RS + j0)     = make_float4(sv[k][0], sv[k][1], sv[k][2], sv[k][3]);
                     *(float4 *)(pl + g * RS + j0 + 4) = make_float4(sv[k][4], sv[k][5], sv[k][6], sv[k][7]);
@@ -622,9 +584,7 @@ __global__ __launch_bounds__(QA_THREADS) void qkv_attn_kernel(const QAParams p) 
         auto chain = [&](const float (&av)[4], const float (&bv)[4], int s0) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float pj = __fmul_rn(bv[i], inv); // p_j = e_j * (float)(1/sum)
-                const float b = __uint_as_float(__float_as_uint(pj) & ((bl && s0 + i < n_it) ? 0xffffffffu : 0u));
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], b, acc, 0, 0, 0);
+                acc = a1_pv_step(acc, av[i], bv[i], inv, bl && s0 + i < n_it); // p_j = e_j * (float)(1/sum)
             }
         };
         if (n_it > 0) {

@@ -15,7 +15,9 @@
 #include "ps_ops.h"
 #include "ps_quant_dev.h"
 
-// the result rows of the Q4_0 / Q8_0 / Q6_K / Q5_K mat-vecs stored write-through like gemv4's (k_gemv4.hip G4_OUT_WT); A/B: -DPS_OUT_WT=0
+// (round 6) the result rows of the producer / chain-wave mat-vecs (k_gemv4.hip, k_gemvb.hip, k_gemvk.hip) are stored write-through: nothing dirty is left for the end-of-kernel
+// write-back, the next launch finds the row in memory; same-box A/B, three rounds (profiles/r06_out_wt_ab.txt): all mat-vecs of a token 1.239 -> 1.226 ms, 8B decode
+// 596.3 -> 599.7 tok/s.  A/B: -DPS_OUT_WT=0
 #ifndef PS_OUT_WT
 #define PS_OUT_WT 1
 #endif
@@ -115,7 +117,31 @@ __device__ __forceinline__ float row_reduce(float acc0, float acc1, float accm) 
 }
 
 
-// ---- shared by the producer / chain-wave kernels with a Q8_K activation (k_gemv4.hip, k_gemvk.hip)
+// ---- the producer / chain-wave kernels' arithmetic that must round where ggml rounds, one copy (k_gemv4.hip, k_gemvb.hip, k_gemvk.hip, the mat-vec half of k_qkvattn.hip).
+// Values in, values out: loops, addresses, barriers and the points where weight requests go out between these steps stay in the kernels (HISTORY.md, round 9).
+// RMSNorm (ggml.c:12667-12720): double sum of squares, scale = 1/sqrtf(mean + eps) from the waves' sums in red[0 .. NW], y = x * (w * scale)
+__device__ __forceinline__ void ch_sumsq4(double &ss, const float4 &v) {
+    ss += (double)__fmul_rn(v.x, v.x);
+    ss += (double)__fmul_rn(v.y, v.y);
+    ss += (double)__fmul_rn(v.z, v.z);
+    ss += (double)__fmul_rn(v.w, v.w);
+}
+template <int NW>
+__device__ __forceinline__ float ch_rms_scale(const double *red, const int K, const float eps) {
+    double tot_ss = 0.0;
+#pragma unroll
+    for (int i = 0; i <= NW; i++) tot_ss += red[i];
+    const float mean = (float)(tot_ss / (double)K);
+    return __fdiv_rn(1.0f, sqrtf(__fadd_rn(mean, eps)));
+}
+__device__ __forceinline__ float ch_norm(const float x, const float w, const float scale) { return __fmul_rn(x, __fmul_rn(w, scale)); }
+// RoPE of element e of a head from the row's value v and its partner's vp (rows 2i, 2i + 1 are a rotation pair), (c, s) of the pair
+__device__ __forceinline__ float ch_rope(const float v, const float vp, const int e, const float c, const float s) {
+    const float x0 = (e & 1) ? vp : v, x1 = (e & 1) ? v : vp;
+    return ps_rope_one(x0, x1, c, s, (e & 1) != 0);
+}
+
+// ---- shared by the producer / chain-wave kernels (k_gemv4.hip, k_gemvb.hip, k_gemvk.hip)
 // silu_hadamard (src/backend/ggml/ggml.cpp:115-129) with glibc's expf table read from LDS: a table lookup in global /
 // constant memory is a vector-memory round trip (> 1 us behind the weight stream) on the chain wave's critical path
 __device__ __forceinline__ float g4_silu_mul(float g, float u, const uint64_t *tab) {
