@@ -465,7 +465,8 @@ __global__ __launch_bounds__(PV_NT) void attn_softmax_pv_kernel(psl_attn_args a)
 // head's workgroups share an XCD, i.e. an L2); every workgroup must be resident (the host checks the grid against the CU
 // count; the poll is bounded and raises sync[31]).
 // LDS: e [4][RS] and V [4][RS] (RS = n_ctx rounded up to 128, + 36: rows 4 banks apart), n_ctx <= 4096.
-// NT threads: 1024, or 512 (tried for its shorter kernel boundary; the per-lane work doubles and the launch measured 0.4 us slower).  LPH = NT / 4 lanes per head take groups of 8 positions: LPH x 8 x TRIPS >= n_ctx
+// NT = 512 threads (the 1024 of the text above were round 3's geometry: a kernel boundary behind 512-thread workgroups costs ~1.5 us less, and since ps_v_expf_n the doubled
+// per-lane work no longer outweighs it: psl_attn_decode2 below).  LPH = NT / 4 lanes per head take groups of 8 positions: LPH x 8 x TRIPS >= n_ctx
 constexpr int D2_MAXCTX = 4096;
 // (round 6) KVS = psl_attn_args::kv_stream: the cached K rows and V channels of a single-token step are read ONCE per token; when the model's whole cache is larger than the
 // memory-side cache nothing of it survives to the next token, and read with plain loads it displaces everything else there and in the L2s: non-temporal loads then
@@ -481,6 +482,7 @@ __device__ __forceinline__ float4 ad2_ld4(const float *p) {
 }
 template <int NV, int NT, int KVS>
 __global__ __launch_bounds__(NT) void attn_decode2_kernel(psl_attn_args a) {
+    static_assert(NT == 512, "the one geometry that production runs (the parameter stays in the list for the instance names of the profile records)");
     constexpr int NW = NT / 64, SPP = NW / 4, LPH = NT / 4, WPH = LPH / 64, D2_TRIPS = D2_MAXCTX / (8 * LPH), VCH = D2_MAXCTX / (4 * NT); // SPP: slices per pass
     extern __shared__ __attribute__((aligned(16))) float d2s[];
     constexpr int hs = NV * 32, RMAX = 16 / NV, G = hs / 4; // G workgroups per kv head; slice (32 positions) s belongs to workgroup s % G
@@ -552,10 +554,7 @@ __global__ __launch_bounds__(NT) void attn_decode2_kernel(psl_attn_args a) {
     mark(2);
     __syncthreads();
 
-    // ---- scores of this workgroup's positions, stored write-through.  ggml_vec_dot_f32 (ggml.c:2092-2133): chain c = 8 a + u runs
-    //      over the elements 32 i + c; here lane tq holds chains 4 tq + e (e = 0..3) with all their steps i.  GGML_F32x8_REDUCE
-    //      (ggml.c:1354-1371): acc0 += acc2, acc1 += acc3 = chain c + chain c + 16 = lane tq + lane tq + 4; acc0 += acc1 = lane + 2;
-    //      low + high 128 bits = lane + 1; then the two hadds inside lane 0: (x0 + x1) + (x2 + x3)
+    // ---- scores of this workgroup's positions (a1_score, ps_attn1_dev.h), stored write-through
     float *const xb = a.xchg + (size_t)kvh * 4 * XS;
 #pragma unroll
     for (int ps = 0; ps < PASSES; ps++) {
@@ -564,24 +563,7 @@ __global__ __launch_bounds__(NT) void attn_decode2_kernel(psl_attn_args a) {
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 if (g < r2) { // (uniform)
-                    // (a1_score of ps_attn1_dev.h, kept as text here: called instead, the <*, 1024, *> instantiations of this kernel compile to three more s_waitcnt each,
-                    //  with or without __restrict__ on q; every other figure and qkv_attn_kernel, which calls it, are unchanged -- HISTORY.md, round 9)
-                    float x[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int m = 0; m < NV; m++) {
-                        const float4 qv = *(const float4 *)(qs + g * hs + m * 32 + 4 * tq);
-                        x[0] = __fmaf_rn(kf[ps][m].x, qv.x, x[0]); // sum = x*y + sum, x = K row (src0)
-                        x[1] = __fmaf_rn(kf[ps][m].y, qv.y, x[1]);
-                        x[2] = __fmaf_rn(kf[ps][m].z, qv.z, x[2]);
-                        x[3] = __fmaf_rn(kf[ps][m].w, qv.w, x[3]);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; e++) x[e] = __fadd_rn(x[e], dpp_f<0x104>(x[e])); // tq < 4: + lane tq + 4
-#pragma unroll
-                    for (int e = 0; e < 4; e++) x[e] = __fadd_rn(x[e], dpp_f<0x102>(x[e])); // tq < 2: + lane tq + 2
-#pragma unroll
-                    for (int e = 0; e < 4; e++) x[e] = __fadd_rn(x[e], dpp_f<0x101>(x[e])); // tq = 0: + lane 1
-                    const float s = __fadd_rn(__fadd_rn(x[0], x[1]), __fadd_rn(x[2], x[3]));
+                    const float s = a1_score<NV>(kf[ps], qs + g * hs + 4 * tq);
                     if (tq == 0) sst[(((uw >> 2) + SPP * ps) * 4 + g) * 32 + (uw & 3) * 8 + p8] = s;
                 }
             }
@@ -1616,33 +1598,20 @@ bool psl_attn_decode2(hipStream_t st, int n_cu, const psl_attn_args &a) {
     if (gx * a.n_kv_heads > n_cu) return false; // every workgroup resident (one per CU at n_ctx = 4096)
     const int RS = ((a.n_ctx + 127) & ~127) + 36;
     const size_t lds = ((size_t)8 * RS + 512 + 128 + 16 + 32 + 4 * a.head_size + (16 * 32 / (a.head_size / 32)) * 4 + 32 + 64) * 4;
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) {
-        (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<4, 1024, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<4, 1024, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<2, 1024, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<2, 1024, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    }
     const dim3 g((unsigned)(gx * a.n_kv_heads));
     // 512-thread workgroups (template parameter NT): a kernel boundary behind them costs ~1.5 us less than behind 1024-thread ones.  Round 3 measured them
     // slower in total (14.05 vs 13.66 us: twice the soft-max numerators per lane, issue-bound); with ps_v_expf_n they win: 8B decode 534.9 -> 542.8 tok/s
-    // (profiles/r04_gemv_variants.txt).  PS_ATTN_NT=1024 brings the round-3 geometry back for an A/B run.
-    static const int nt_env = getenv("PS_ATTN_NT") ? atoi(getenv("PS_ATTN_NT")) : 512;
-    psk_note_attn("attn_decode2_kernel<%d, %d, %d>", a.head_size / 32, nt_env == 512 ? 512 : 1024, a.kv_stream ? 1 : 0);
-    static unsigned long long attr5 = 0;
-    if (ps_first_on_device(&attr5)) {
+    // (profiles/r04_gemv_variants.txt); the 1024-thread instances left with round 12.
+    psk_note_attn("attn_decode2_kernel<%d, %d, %d>", a.head_size / 32, 512, a.kv_stream ? 1 : 0);
+    static unsigned long long attr = 0; // devices that have the attribute
+    if (ps_first_on_device(&attr)) {
         (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<4, 512, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
         (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<4, 512, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
         (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<2, 512, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
         (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<2, 512, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     }
-    if (nt_env == 512) {
-        if (a.head_size == 128) { if (a.kv_stream) hipLaunchKernelGGL((attn_decode2_kernel<4, 512, 1>), g, dim3(512), lds, st, a); else hipLaunchKernelGGL((attn_decode2_kernel<4, 512, 0>), g, dim3(512), lds, st, a); }
-        else { if (a.kv_stream) hipLaunchKernelGGL((attn_decode2_kernel<2, 512, 1>), g, dim3(512), lds, st, a); else hipLaunchKernelGGL((attn_decode2_kernel<2, 512, 0>), g, dim3(512), lds, st, a); }
-        return true;
-    }
-    if (a.head_size == 128) { if (a.kv_stream) hipLaunchKernelGGL((attn_decode2_kernel<4, 1024, 1>), g, dim3(1024), lds, st, a); else hipLaunchKernelGGL((attn_decode2_kernel<4, 1024, 0>), g, dim3(1024), lds, st, a); }
-    else { if (a.kv_stream) hipLaunchKernelGGL((attn_decode2_kernel<2, 1024, 1>), g, dim3(1024), lds, st, a); else hipLaunchKernelGGL((attn_decode2_kernel<2, 1024, 0>), g, dim3(1024), lds, st, a); }
+    if (a.head_size == 128) { if (a.kv_stream) hipLaunchKernelGGL((attn_decode2_kernel<4, 512, 1>), g, dim3(512), lds, st, a); else hipLaunchKernelGGL((attn_decode2_kernel<4, 512, 0>), g, dim3(512), lds, st, a); }
+    else { if (a.kv_stream) hipLaunchKernelGGL((attn_decode2_kernel<2, 512, 1>), g, dim3(512), lds, st, a); else hipLaunchKernelGGL((attn_decode2_kernel<2, 512, 0>), g, dim3(512), lds, st, a); }
     return true;
 }
 

@@ -33,7 +33,7 @@
 // fp16 A operands, d and dmin as fp32 -- is made ONCE per super-block (producer h: accumulator lanes 2h, 2h + 1 of all 32
 // rows; lane = (row, k-group pair)) and parked in LDS ahead of the consumers, one barrier per pair of steps.  The producers
 // own their memory pipeline: a register ring of G4K_RING super-blocks is in flight from HBM, nobody waits on a weight load.
-// (Round-2 history, tools/g4k_exp.py and tools/gpu_g4k_timeline.py: a per-wave int8 version -- scale split 8 hi + lo, two
+// (Round-2 history, a prefill timer and tools/gpu_g4k_timeline.py: a per-wave int8 version -- scale split 8 hi + lo, two
 // v_mfma_i32_16x16x32_i8 with a shift between -- spent a third of its vector instructions on the shared derivations and,
 // once those had moved to producers, 64 of its remaining 176 instructions per step on the shifts and conversions the fp16
 // form does not have.)
@@ -455,9 +455,6 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm4k_kernel(const G4
             if (!(sb & 1)) __syncthreads(); // the producers have parked this step and the next
             mark(sb);
             g4k_superblock<WT>(T, lds + (sb & (G4K_NST - 1)) * G4K_STAGE, zero, B, qf_ct + ((size_t)nb << 13), M, m, kb, uh);
-#ifdef G4K_MARK2
-            if (dbg) { asm volatile("" : "+v"(T.acc[0][0][0]), "+v"(T.acc[1][3][1]), "+v"(T.accm[1][1][1])); mark(sb); } // (the step's chains done)
-#endif
             M = Mn;
         };
         for (int sb = 0; sb < p.nsb - 1; sb++) step(sb);
@@ -983,6 +980,7 @@ int g_g4k_par = getenv("PS_GEMM4K_PAR") ? atoi(getenv("PS_GEMM4K_PAR")) : 1; // 
 // exchange through LDS at the end.
 template <int EPI, int RA, int MB> // MB: waves per SIMD the register allocation leaves room for
 __global__ __launch_bounds__(EPI == 1 ? 128 : 64, MB) void gemm4k_wav_kernel(const G4KParams p) {
+    static_assert(RA == 2 && MB == 2, "the one ring depth and occupancy that production runs (the parameters stay in the list for the instance names of the profile records)");
     const int wave = EPI == 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0, lane = threadIdx.x & 63;
     const int m = lane & 15, kb = lane >> 4;
     __shared__ float xup[EPI == 1 ? 64 * 4 : 1];
@@ -1034,7 +1032,6 @@ __global__ __launch_bounds__(EPI == 1 ? 128 : 64, MB) void gemm4k_wav_kernel(con
     const g4k_f4 zf = {0.f, 0.f, 0.f, 0.f};
     const g4k_h2 k1024 = {(_Float16)1024.f, (_Float16)1024.f}, km1024 = {(_Float16)-1024.f, (_Float16)-1024.f};
     const uint32_t sel0 = 0x04000400u | ((uint32_t)(2 * (kb & 1)) * 0x00010001u), sel1 = sel0 + 0x00010001u; // scales 2 (kb & 1), + 1 of the four
-    static_assert(RA % 2 == 0, "the 16-sum ring is two deep");
 #pragma clang loop unroll(disable)
     for (int sb0 = 0; sb0 < nsb; sb0 += RA) { // (nsb % RA == 0: the host checks)
 #pragma unroll
@@ -1393,8 +1390,7 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
     // 8B tree forward, ms by width (profiles/r02_tree_forward_latency_8b.json): 2: 4.7, 8: 4.7, 12: 4.8, 16: 4.8 (narrow kernel),
     // 32: 5.9, 64: 6.3, 128: 8.4 (wide); the round-1 kernels that spread a row group's integer work over producer waves
     // (gemm8): 2: 4.9, 8: 5.0, 12: 6.1, 16: 6.2, 32: 8.8, 64: 12.8, 96: 19.9.  PS_GEMM4K_MIN_COLS moves the switch (default 2, psk_gemm4k_frag).
-    static const bool no_wav = getenv("PS_NO_GEMM4K_WAV") != nullptr;                                     // (A/B switches for measurements)
-    static const int wav_cfg = getenv("PS_GEMM4K_WAV_CFG") ? atoi(getenv("PS_GEMM4K_WAV_CFG")) : 0;
+    static const bool no_wav = getenv("PS_NO_GEMM4K_WAV") != nullptr; // (A/B switch for measurements)
     const int par_cfg = g_g4k_par; // 0: off, 4 / 8: that many waves per tile, else by tile count
     const int ctw = n_ct <= 1 ? 1 : 4; // column tiles per workgroup: the narrow kernel for at most 16 columns (its two-tile form, CT = 2, spills: 13.7 ms per 8B forward against 5.9 ms, not instantiated)
     p.n_cb = (n_ct + ctw - 1) / ctw;
@@ -1425,7 +1421,7 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
     if (p.wt == PS_Q5_K) { // (single matrix, EPI 0)
         if (ctw == 1) { psk_note_kernel("gemm4k_narrow_kernel<0, 1, 13>"); hipLaunchKernelGGL((gemm4k_narrow_kernel<0, 1, PS_Q5_K>), grid, blkn, LDS1, st, p); }
         else { psk_note_kernel("gemm4k_kernel<0, 13>"); hipLaunchKernelGGL((gemm4k_kernel<0, PS_Q5_K>), grid, blk, G4K_LDS, st, p); }
-    } else if (ctw == 1 && n_ct == 1 && !no_wav && epi != 1 && par_cfg != 0 && !(2 * p.n_tasks >= 4 * n_cu || wav_cfg == 1)) {
+    } else if (ctw == 1 && n_ct == 1 && !no_wav && epi != 1 && par_cfg != 0 && 2 * p.n_tasks < 4 * n_cu) {
         // at most 16 columns, few row tiles (Q / K / V, O, down of a tree batch): the super-blocks of a round side by side, the chains behind them
         // (any nsb).  8B, 12 wide, us per launch, four waves walking K -> this: see profiles/r04_tree12_kernel_stats.txt
         static unsigned long long attrp = 0;
@@ -1445,9 +1441,9 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
         // super-block step whatever was tried on it: its LDS operands fetched a step ahead (16.7 us average per launch, as before), the
         // header operands derived once by the parking wave instead of by all four (170 -> ~110 instructions per step: 16.6 us), a fifth
         // wave that owns the HBM stream with an eight-deep fragment ring in the others (22.9 us).
+        // EPI 0 comes here with many tiles (lm_head: a wave per tile, occupancy hides the latency) and, A/B only, with few tiles under PS_GEMM4K_PAR=0
         if (epi == 1) g4k_launch_wav<1, 2, 2>(st, p);
-        else if (2 * p.n_tasks >= 4 * n_cu || wav_cfg == 1) g4k_launch_wav<0, 2, 2>(st, p); // many tiles (lm_head): a wave per tile, occupancy hides the latency
-        else g4k_launch_wav<0, 2, 2>(st, p); // few tiles with PS_GEMM4K_PAR=0 (A/B only; round 3's four-waves-per-tile kernel for this case was removed in round 5: gemm4k_par_kernel covers it)
+        else g4k_launch_wav<0, 2, 2>(st, p);
     } else if (ctw == 1) {
         if (epi == 1) { psk_note_kernel("gemm4k_narrow_kernel<1, 1, 12>"); hipLaunchKernelGGL((gemm4k_narrow_kernel<1, 1, PS_Q4_K>), grid, blkn, LDS1, st, p); }
         else { psk_note_kernel("gemm4k_narrow_kernel<0, 1, 12>"); hipLaunchKernelGGL((gemm4k_narrow_kernel<0, 1, PS_Q4_K>), grid, blkn, LDS1, st, p); }

@@ -16,7 +16,6 @@
 #include "ps_g4_dev.h"
 
 namespace {
-constexpr int G4_PAIR = 0; // units of a chunk the scheduler may interleave (0: one at a time)
 
 struct G4Mat {
     const uint8_t *qs, *aux;
@@ -41,13 +40,16 @@ struct G4Params {
     int rope_wi0;               // EPI 2: w[0]'s place in the Q / K / V triple (a launch may carry a part of it)
 };
 
-// NW producer waves, DC chunks of weight loads in flight per wave (register ring), TPW activation tiles per producer,
-// XW: wait for the activation row before the first weight request goes out (short launches: the row does not queue
-// behind the whole chip's first burst of weights)
+// NW producer waves, TPW activation tiles per producer.
+// DC = 2 chunks of weight loads in flight per wave (register ring) and XW = 2 (staged issue, below) are the only values left: the parameters stay in the
+// list so that the instance names of the profile records keep naming the same kernels.  Rings of 3 and 4 chunks, everything issued up front (XW 0),
+// chunk 1 at the sum-of-squares barrier (XW 1) and a split issue of the steady state (XW 3) were swept in rounds 2-4 and none beat this one
+// (profiles/r02_gemv4_variants.txt, profiles/r04_gemv_variants.txt; the LDS-DMA form is tools/experiments/r04_k_gemv7.hip).
 // YS: the activation operands of a wave's units stay in registers (1: the wave meets the same four super-blocks in every chunk,
-// UPB % tot == 0; 2: two alternating sets, one per ring slot, 2 UPB % tot == 0 and DC == 2; 0: fetched from LDS per unit)
+// UPB % tot == 0; 0: fetched from LDS per unit).  Two alternating operand sets (YS 2, 2 UPB % tot == 0) measured no gain (profiles/r04_gemv_variants.txt).
 template <int NW, int DC, int TPW, int XW, int EPI, int PRO, int YS = 0>
 __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) {
+    static_assert(DC == 2 && XW == 2 && YS <= 1, "the one ring shape and issue order that production runs");
     constexpr int WT = PS_Q4_K;
     using TR  = WTraits<WT>;
     // record of one (unit, lane): {d * yd, (float)sumi, -dmin * yd, (float)(mins . bsums)} -- everything up to the two
@@ -121,7 +123,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
         const uint32_t lane16 = (uint32_t)lane * 16u;
         // loads are UNCONDITIONAL (a slot past the range re-reads the workgroup's first unit) so that the compiler counts
         // vmcnt exactly and a chunk is consumed while the next ones are in flight
-        auto issue = [&](ps_u32x4 (&q)[UPW], ps_u32x4 &h, int tl, int un, int i_lo = 0, int i_hi = UPW) { // units [i_lo, i_hi) of the slot; the header piece rides with unit 0
+        auto issue = [&](ps_u32x4 (&q)[UPW], ps_u32x4 &h, int tl, int un) {
             const bool live = tl < nt;
             int grp = t0 + (live ? tl : 0), ul = live ? un : 0;
             const uint8_t *qb = p.w[0].qs, *ab = p.w[0].aux;
@@ -136,41 +138,35 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
             // a dead slot costs one cache line: every lane asks for the same 16 bytes of the workgroup's first unit
             const uint32_t lo = live ? lane16 : 0u, st = live ? 1u : 0u;
 #pragma unroll
-            for (int i = 0; i < UPW; i++)
-                if (i >= i_lo && i < i_hi) q[i] = __builtin_nontemporal_load((const ps_u32x4 *)(qg + i * (1024 * st) + lo));
-            if (i_lo == 0) h = *(const ps_u32x4 *)(ag + (live ? (uint32_t)(lane & 31) * 16u : 0u)); // (plain: with the non-temporal hint the fused launch gains 0.3 us, these launches nothing -- ps_gemv_dev.h G4_HDR_NT)
+            for (int i = 0; i < UPW; i++) q[i] = __builtin_nontemporal_load((const ps_u32x4 *)(qg + i * (1024 * st) + lo));
+            h = *(const ps_u32x4 *)(ag + (live ? (uint32_t)(lane & 31) * 16u : 0u)); // (plain: with the non-temporal hint the fused launch gains 0.3 us, these launches nothing -- ps_gemv_dev.h G4_HDR_NT)
         };
-        constexpr int YN = YS ? YS : 1;
-        int4 Y0[YN][UPW], Y1[YN][UPW];
-        int2 YB[YN][UPW];
-        float YD[YN][UPW];
-        int yset = 0; // (a constant once the ring loop is unrolled)
-        auto produce = [&](const ps_u32x4 (&q)[UPW], const ps_u32x4 &hc, int tl, int un, int buf, int i_lo = 0, int i_hi = UPW) {
+        int4 Y0[UPW], Y1[UPW]; // (YS)
+        int2 YB[UPW];
+        float YD[UPW];
+        auto produce = [&](const ps_u32x4 (&q)[UPW], const ps_u32x4 &hc, int tl, int un, int buf) {
             if (tl >= nt) return; // wave-uniform: nothing of this chunk belongs to the wave
             const int ul = (EPI == 1 && un >= n_units) ? un - n_units : un;
-            if (i_lo == 0 && lane < 32) g4_expand_header(hc, hscr[wave] + lane * G4_HX); // lane l loaded the header of (unit l >> 3, row l & 7)
+            if (lane < 32) g4_expand_header(hc, hscr[wave] + lane * G4_HX); // lane l loaded the header of (unit l >> 3, row l & 7)
 #pragma unroll
             for (int i = 0; i < UPW; i++) {
-                if (i < i_lo || i >= i_hi) continue;
-                recs[(buf * UPB + wave * UPW + i) * 64 + lane] = YS ? g4_unit_y(q[i], hscr[wave] + (i * 8 + r) * G4_HX, u, Y0[yset][i], Y1[yset][i], YB[yset][i], YD[yset][i])
+                recs[(buf * UPB + wave * UPW + i) * 64 + lane] = YS ? g4_unit_y(q[i], hscr[wave] + (i * 8 + r) * G4_HX, u, Y0[i], Y1[i], YB[i], YD[i])
                                                                     : g4_unit(q[i], hscr[wave] + (i * 8 + r) * G4_HX, ul + i, u, A); // (lanes u >= 4: .w is not a product, their acc_m is never read)
-                if (G4_PAIR == 0 || (i & 1)) __builtin_amdgcn_sched_barrier(0); // one unit (G4_PAIR: two) at a time: interleaving four of them costs registers, hides nothing
+                __builtin_amdgcn_sched_barrier(0); // one unit at a time: interleaving them costs registers, hides nothing
             }
         };
         auto advance = [&](int &tl, int &un) {
             tl += step_t; un += step_u;
             if (un >= tot) { un -= tot; tl++; }
         };
-        // XW (staged issue): only chunk 0 goes out before the prologue.  XW 1: chunk 1 at the sum-of-squares barrier, XW 2 (production):
-        // chunk 1 behind the quantizer as well — at the barrier the CU's queue still holds every wave's chunk 0, the waves
-        // stalled ~0.9 us IN that issue, on the critical path of the prologue (activation in LDS after 3.1 instead of 4.0 us;
-        // gate/up 17.3 -> 16.1 us).  XW 3 adds the split issue of the steady state (no gain, kept for the sweep).  The CU's vector-memory queue is served in order at
-        // 64 B per clock and a wave whose requests do not fit stalls IN the issue: with two chunks (16 KiB + headers per
+        // Staged issue: with a prologue (PRO != 0) only chunk 0 goes out before it and chunk 1 follows behind the quantizer.  The CU's vector-memory
+        // queue is served in order at 64 B per clock and a wave whose requests do not fit stalls IN the issue: with both chunks (16 KiB + headers per
         // wave) up front the waves spent 1.2 us issuing before they could look at the activation row, and the slowest
-        // reached the sum-of-squares barrier 1 us after the first.  The later chunks follow behind the prologue's barriers.
-        constexpr bool STAGED = XW && PRO != 0;
+        // reached the sum-of-squares barrier 1 us after the first.  Chunk 1 at the sum-of-squares barrier was tried too: the CU's queue still holds
+        // every wave's chunk 0 there and the waves stalled ~0.9 us in that issue, on the critical path of the prologue (activation in LDS after
+        // 3.1 instead of 4.0 us, gate/up 17.3 -> 16.1 us: profiles/r04_gemv_variants.txt, the timelines profiles/r04_gemv_timeline_cfg*.txt).
         issue(q[0], h[0], tS[0], uS[0]);
-        if (!STAGED) {
+        if (PRO == 0) { // (no prologue to hide behind: the rest of the ring at once)
 #pragma unroll
             for (int d = 1; d < DC; d++) issue(q[d], h[d], tS[d], uS[d]);
         }
@@ -206,7 +202,6 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
                 if (lane == 0) red[wave] = ss;
                 __syncthreads();
                 pmark(25);
-                if (STAGED && XW == 1 && DC > 1) issue(q[1], h[1], tS[1], uS[1]); // (XW 2, 3: after the quantizer instead, with the others)
                 scale = ch_rms_scale<NW>(red, K, p.eps);
                 pmark(26);
             }
@@ -223,48 +218,29 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
                 g4_quantize_pair(v, tp * 512 + lane * 8, tp, lq, ld, lb, live);
             }
             pmark(27);
-            if (STAGED) {
 #pragma unroll
-                for (int d = ((PRO == 1 && XW == 1) ? 2 : 1); d < DC; d++) issue(q[d], h[d], tS[d], uS[d]);
-            }
+            for (int d = 1; d < DC; d++) issue(q[d], h[d], tS[d], uS[d]); // (a loop, not q[1]: written out, the compiler schedules the requests differently)
             __syncthreads();
         }
         mark(); // 2: activation in LDS
-        if (YS) { // this wave's activation operands: set k = the units of chunk k
+        if (YS) { // this wave's activation operands: the units of chunk 0 are the units of every chunk
+            const int un = uS[0], ul = (EPI == 1 && un >= n_units) ? un - n_units : un;
 #pragma unroll
-            for (int k = 0; k < YN; k++) {
-                const int un = uS[k], ul = (EPI == 1 && un >= n_units) ? un - n_units : un;
-#pragma unroll
-                for (int i = 0; i < UPW; i++) {
-                    Y0[k][i] = *(const int4 *)(A.q32 + (ul + i) * 64 + u * 8);
-                    Y1[k][i] = *(const int4 *)(A.q32 + (ul + i) * 64 + u * 8 + 4);
-                    YB[k][i] = *(const int2 *)(A.bs32 + (ul + i) * 8 + 2 * (u & 3));
-                    YD[k][i] = A.d[ul + i];
-                }
+            for (int i = 0; i < UPW; i++) {
+                Y0[i] = *(const int4 *)(A.q32 + (ul + i) * 64 + u * 8);
+                Y1[i] = *(const int4 *)(A.q32 + (ul + i) * 64 + u * 8 + 4);
+                YB[i] = *(const int2 *)(A.bs32 + (ul + i) * 8 + 2 * (u & 3));
+                YD[i] = A.d[ul + i];
             }
         }
         // 4. chunk it * DC + d from ring slot d
         for (int it = 0; it < n_iters; it++) {
 #pragma unroll
             for (int d = 0; d < DC; d++) {
-                yset = YS == 2 ? d : 0;
-                if constexpr (XW == 3) {
-                    // split issue: the registers of a slot's first two units are free once those units are produced, so
-                    // their next loads go out half a chunk earlier (more bytes in flight while this chunk is being produced,
-                    // without a deeper ring)
-                    const int tl_now = tS[d], un_now = uS[d];
-                    advance(tS[d], uS[d]);
-                    produce(q[d], h[d], tl_now, un_now, (it * DC + d) & 1, 0, 2);
-                    issue(q[d], h[d], tS[d], uS[d], 0, 2);
-                    produce(q[d], h[d], tl_now, un_now, (it * DC + d) & 1, 2, 4);
-                    mark(); // 3, 6, ...: chunk produced
-                    issue(q[d], h[d], tS[d], uS[d], 2, 4);
-                } else {
-                    produce(q[d], h[d], tS[d], uS[d], (it * DC + d) & 1);
-                    mark(); // 3, 6, ...: chunk produced
-                    advance(tS[d], uS[d]);
-                    issue(q[d], h[d], tS[d], uS[d]);
-                }
+                produce(q[d], h[d], tS[d], uS[d], (it * DC + d) & 1);
+                mark(); // 3, 6, ...: chunk produced
+                advance(tS[d], uS[d]);
+                issue(q[d], h[d], tS[d], uS[d]);
                 mark(); // 4, 7, ...: next loads issued
                 __syncthreads();
                 mark(); // 5, 8, ...: barrier passed
@@ -436,9 +412,6 @@ int launch_g4_kc(hipStream_t st, int grid, const G4Params &p, int epi, int pro) 
 
 } // namespace
 
-int g_g4_cfg = getenv("PS_G4_CFG") ? atoi(getenv("PS_G4_CFG")) : 0; // ps_hip_debug_set(1, cfg)  (cfg 20..23 were round 4's LDS-DMA kernel: tools/experiments/r04_k_gemv7.hip)
-int g_g4_flags = 0; // ps_hip_debug_set(2, flags): reserved for what-if switches
-
 bool psk_gemv4_takes(const psk_gemv_args &a, int64_t K, int64_t bs) { // rows end on multiples of four units
     static const bool off = getenv("PS_NO_GEMV4") != nullptr; // (A/B switch for measurements)
     if (off || bs != 1 || a.n_w < 1 || a.n_w > 3 || K % 1024 || K > 16384) return false;
@@ -467,36 +440,16 @@ int psk_gemv4(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int6
     const int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
     p.split_q = p.n_tasks / grid; p.split_r = p.n_tasks % grid;
     p.dbg = psk_gemv_dbg_buf(epi, (epi == 0 && a.pro == 2 && K <= a.w[0]->N) ? 3 : a.pro); // timeline keys: 9 QKV, 3 O (K <= N), 5 gate/up, 2 down
-    // wave configuration (measured, tools/g4_variants.py): rows of a multiple of 7 units take 7 (14) producers
+    // wave configuration (measured in rounds 2-4, profiles/r04_gemv_variants.txt): rows of a multiple of 7 units take 7 producers
     const bool seven = p.n_units % 7 == 0;
-    if (g_g4_cfg == 40 || g_g4_cfg == 41) { // register-resident activation operands on the register ring (41: three chunks in flight)
-        const int tot = (epi == 1 ? 2 : 1) * p.n_units, upb = (seven ? 7 : 8) * 4;
-        const int ys = upb % tot == 0 ? 1 : ((2 * upb) % tot == 0 ? 2 : 0);
-        if (ys == 1 && g_g4_cfg == 41 && !seven) return launch_g4_kc<8, 3, 2, 1>(st, grid, p, epi, a.pro);
-        if (ys == 1) return seven ? launch_g4_kc<7, 2, 2, 1>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 2, 2, 1>(st, grid, p, epi, a.pro);
-        if (ys == 2) return seven ? launch_g4_kc<7, 2, 2, 2>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 2, 2, 2>(st, grid, p, epi, a.pro);
-    }
-    switch (g_g4_cfg) { // (0 is the production configuration; the others are kept for tools/g4_variants.py)
-    case 1: return seven ? launch_g4_kc<7, 2, 0>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 2, 0>(st, grid, p, epi, a.pro); // everything issued up front
-    case 2: return seven ? launch_g4_kc<7, 3, 1>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 3, 1>(st, grid, p, epi, a.pro); // three chunks in flight
-    case 3: return launch_g4_kc<11, 2, 1>(st, grid, p, epi, a.pro);                                                          // twelve waves
-    case 12: return launch_g4_kc<10, 2, 2>(st, grid, p, epi, a.pro);
-    case 13: return launch_g4_kc<11, 2, 2>(st, grid, p, epi, a.pro);
-    case 14: return launch_g4_kc<12, 2, 2>(st, grid, p, epi, a.pro);
-    case 7: return seven ? launch_g4_kc<7, 2, 3>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 2, 3>(st, grid, p, epi, a.pro); // + split issue
-    case 6: return seven ? launch_g4_kc<7, 3, 2>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 3, 2>(st, grid, p, epi, a.pro);
-    case 4: return seven ? launch_g4_kc<7, 4, 1>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 4, 1>(st, grid, p, epi, a.pro); // four chunks in flight
-    case 8: return seven ? launch_g4_kc<7, 2, 1>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 2, 1>(st, grid, p, epi, a.pro); // chunk 1 at the sum-of-squares barrier (round-2 default until the timeline showed the stall)
-    default:
-        // register-resident activation operands (YS = 1) where a wave meets the same four super-blocks in every chunk and the stream is long
-        // enough to pay for fetching them once: gate/up and the lm_head of a K = 4096 model (round 4, profiles/r04_gemv_variants.txt:
-        // gate/up 16.1 -> 15.4 us, lm_head 51.4 -> 50.0 us with 8 producers; the one- and two-chunk launches did not move)
-        if (!seven && (8 * 4) % ((epi == 1 ? 2 : 1) * p.n_units) == 0 && (epi == 1 || (a.n_w == 1 && p.split_q >= 32)) && g_g4_cfg != 42)
-            return launch_g4_kc<8, 2, 2, 1>(st, grid, p, epi, a.pro);
-        // eleven producers where the stream per workgroup is long and there is one matrix (down: K = 14336; lm_head: 63 row
-        // groups per workgroup): 45 KB per chunk in flight instead of 29-37 (down 12.2 -> 11.6 us, lm_head 54.5 -> 51 us);
-        // the short launches and gate/up measured slower with them (QKV 7.5 -> 9.1 us: prologue and boundary of 768 threads)
-        if (epi == 0 && a.n_w == 1 && (seven || p.split_q >= 32)) return launch_g4_kc<11, 2, 2>(st, grid, p, epi, a.pro);
-        return seven ? launch_g4_kc<7, 2, 2>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 2, 2>(st, grid, p, epi, a.pro);
-    }
+    // register-resident activation operands (YS = 1) where a wave meets the same four super-blocks in every chunk and the stream is long
+    // enough to pay for fetching them once: gate/up and the lm_head of a K = 4096 model (round 4, profiles/r04_gemv_variants.txt:
+    // gate/up 16.1 -> 15.4 us, lm_head 51.4 -> 50.0 us with 8 producers; the one- and two-chunk launches did not move)
+    if (!seven && (8 * 4) % ((epi == 1 ? 2 : 1) * p.n_units) == 0 && (epi == 1 || (a.n_w == 1 && p.split_q >= 32)))
+        return launch_g4_kc<8, 2, 2, 1>(st, grid, p, epi, a.pro);
+    // eleven producers where the stream per workgroup is long and there is one matrix (down: K = 14336; lm_head: 63 row
+    // groups per workgroup): 45 KB per chunk in flight instead of 29-37 (down 12.2 -> 11.6 us, lm_head 54.5 -> 51 us);
+    // the short launches and gate/up measured slower with them (QKV 7.5 -> 9.1 us: prologue and boundary of 768 threads)
+    if (epi == 0 && a.n_w == 1 && (seven || p.split_q >= 32)) return launch_g4_kc<11, 2, 2>(st, grid, p, epi, a.pro);
+    return seven ? launch_g4_kc<7, 2, 2>(st, grid, p, epi, a.pro) : launch_g4_kc<8, 2, 2>(st, grid, p, epi, a.pro);
 }

@@ -13,8 +13,9 @@
 //     the prologue (quad-major tiles in LDS: a lane's eight activation dwords of a unit are two ds_read_b128);
 //   * Q6_K's  sum (q - 32) y  needs no correction term: (q ^ 32) << 2 IS the signed byte 4 (q - 32), v_dot4 returns four
 //     times the sum and the unit's int32 is shifted back once;
-//   * a register ring of DC chunks of UPW units per producer (default 3 chunks of 2: 80 KB of Q6_K in flight per CU), the first chunk
-//     requested before the prologue, the others behind the quantizer.
+//   * a register ring of DC = 3 chunks of UPW = 2 units per producer (80 KB of Q6_K in flight per CU), the first chunk
+//     requested before the prologue, the others behind the quantizer.  Rings of 2 x 3, 4 x 2, 3 x 2 with two early chunks and 6 x 1 measured
+//     slower (8B Q5_K_M 394-414 tok/s against 422: HISTORY.md, round 3).
 // Epilogues as gemv4: EPI 0 bias / residual, EPI 1 SiLU(gate) * up, EPI 2 adjacent-pair RoPE + KV-cache append (Q / K / V).
 #include "ps_gemv_dev.h"
 
@@ -50,9 +51,11 @@ struct GKParams {
 };
 
 // NW producer waves, UPW units per producer and chunk, DC chunks in flight per producer (EA of them requested before the
-// prologue), TPW activation tiles per producer
+// prologue), TPW activation tiles per producer.  UPW = 2, DC = 3, EA = 1 is the one ring left; the parameters stay so that the instance names
+// of the profile records keep naming the same kernels.
 template <int WT, int NW, int UPW, int DC, int EA, int TPW, int EPI, int PRO>
 __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) {
+    static_assert(UPW == 2 && DC == 3 && EA == 1, "the one ring shape that production runs");
     using Rec = typename GKRec<WT>::T;
     constexpr int UPB = NW * UPW;
     constexpr bool MULTI = WT != PS_Q6_K; // several matrices per launch (Q6_K launches carry one: no per-lane matrix selects)
@@ -420,14 +423,7 @@ int launch_gk_kc(hipStream_t st, int grid, const GKParams &p, int epi, int pro) 
 }
 template <int WT>
 int launch_gk_wt(hipStream_t st, int grid, const GKParams &p, int epi, int pro) {
-    static const int cfg = getenv("PS_GEMVK_CFG") ? atoi(getenv("PS_GEMVK_CFG")) : 0; // (ring shape, for measurements)
-    switch (cfg) {
-    case 1: return launch_gk_kc<WT, 3, 2, 1>(st, grid, p, epi, pro); // 8B Q5_K_M 390 tok/s against 413 with the default, Q4_K_M 452 / 457
-    case 2: return launch_gk_kc<WT, 2, 4, 1>(st, grid, p, epi, pro);
-    case 3: return launch_gk_kc<WT, 2, 3, 2>(st, grid, p, epi, pro);
-    case 4: return launch_gk_kc<WT, 1, 6, 2>(st, grid, p, epi, pro);
-    default: return launch_gk_kc<WT, 2, 3, 1>(st, grid, p, epi, pro);
-    }
+    return launch_gk_kc<WT, 2, 3, 1>(st, grid, p, epi, pro);
 }
 
 } // namespace

@@ -262,3 +262,25 @@ def test_kv_interface_members(ctx, oracle, tmp_path):
     assert gm.kv_append_tokens(1) == 4 and gm.position == 5
     assert ctx.L.ps_hip_model_kv_save_tokens(gm.h, 10_000) == 2
     gm.close()
+
+
+def test_removed_debug_keys_are_unknown_and_leave_the_mat_vec_alone(ctx, oracle):
+    """ps_hip_debug_set keys 1 and 2 (the decode mat-vec's wave configuration and a what-if word) left with the kernel configurations they selected:
+    they answer like any unknown key, and nothing of them stays behind -- a Q4_K single column (K = 1024, N = 64: the smallest shape gemv4 takes)
+    still runs gemv4_kernel and is bit-equal to the oracle."""
+    from powerserve_amd import synth
+    assert ctx.L.ps_hip_debug_set(99, 0) != 0
+    assert ctx.L.ps_hip_debug_set(1, 0) != 0
+    assert ctx.L.ps_hip_debug_set(2, 0) != 0
+    K, N = 1024, 64
+    rng = np.random.default_rng(12)
+    w = synth.random_blocks(rng, 12, N, K)
+    x = rng.standard_normal((1, K)).astype(np.float32)
+    want = oracle.mul_mat(12, w, K, N, x)
+    W = ctx.upload_weight(12, w, K, N)
+    dx, dy = ctx.to_device(x), ctx.empty((1, N))
+    ctx.check(ctx.L.ps_hip_mul_mat(ctx.h, C.byref(dy.tensor()), C.byref(W.tensor()), C.byref(dx.tensor())))
+    got = dy.numpy()
+    assert np.array_equal(bits(got), bits(want)), np.flatnonzero(bits(got) != bits(want))[:8]
+    assert ctx.L.ps_hip_last_matmul_kernel().decode().startswith("gemv4_kernel<")
+    W.free()

@@ -16,7 +16,6 @@ d = tempfile.mkdtemp(prefix="ps_atl_")
 synth.write_model_dir(d, "llama-8b-dims-4l", 12, n_ctx=4096, seed=1)
 ctx = hip.Ctx(0)
 m = hip.Model(ctx, d, max_batch=128, n_ctx=4096)
-ctx.check(ctx.L.ps_hip_debug_set(2, int(os.environ.get("G4_FLAGS", "0"))))
 rng = np.random.default_rng(0)
 for lo in range(0, P, 128):
     m.forward(rng.integers(0, 4096, 128), np.arange(lo, lo + 128), lm_head=False)

@@ -17,8 +17,6 @@ d = tempfile.mkdtemp(prefix="ps_tl_")
 synth.write_model_dir(d, "llama-8b-dims-4l", 12, n_ctx=4096, seed=1)
 ctx = hip.Ctx(0)
 m = hip.Model(ctx, d, max_batch=128, n_ctx=4096)
-ctx.check(ctx.L.ps_hip_debug_set(1, int(os.environ.get("G4_CFG", "0"))))
-ctx.check(ctx.L.ps_hip_debug_set(2, int(os.environ.get("G4_FLAGS", "0"))))
 mode = int(os.environ.get("TL_MODE", "0"))
 prompt = np.random.default_rng(1).integers(0, m.cfg.vocab_size, n_prompt).astype(np.int32)
 done = 0

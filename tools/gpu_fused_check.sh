@@ -11,5 +11,5 @@ DB=$(find gpurun_out/prof_kt -name "*.db" | head -1)
 python tools/prof_summary.py $DB --decode > gpurun_out/r06_decode_kernel_stats_fused.txt 2>&1
 head -8 gpurun_out/r06_decode_kernel_stats_fused.txt
 rm -rf gpurun_out/prof_kt
-timeout 300 python tools/g4_variants.py 0 0 2>&1 | tail -2 | tee gpurun_out/r06_fused_ab.txt
-echo "== two launches"; PS_NO_QKV_ATTN=1 timeout 300 python tools/g4_variants.py 0 2>&1 | tail -1 | tee -a gpurun_out/r06_fused_ab.txt
+timeout 300 python bench.py --steps 32 --warmup 4 2>/dev/null | tail -1 | cut -c1-200 | tee $O/r06_fused_ab.txt
+echo "== two launches"; PS_NO_QKV_ATTN=1 timeout 300 python bench.py --steps 32 --warmup 4 2>/dev/null | tail -1 | cut -c1-200 | tee -a $O/r06_fused_ab.txt

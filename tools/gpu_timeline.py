@@ -16,7 +16,6 @@ d = tempfile.mkdtemp(prefix="ps_tl_")
 synth.write_model_dir(d, "llama-8b-dims-4l", 12, n_ctx=512, seed=1)
 ctx = hip.Ctx(0)
 m = hip.Model(ctx, d, max_batch=8, n_ctx=512)
-ctx.check(ctx.L.ps_hip_debug_set(1, int(os.environ.get('G4_CFG', '0'))))
 mode = int(os.environ.get('TL_MODE', '1'))  # 1 eager launches, 0 hipGraph replay
 m.set_mode(mode)
 if mode == 0:

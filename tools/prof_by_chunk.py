@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel average duration by call order (rocprofv3 rocpd database): the calls of each kernel are split into `groups` equal
-runs in start order -- with tools/g4k_exp.py (2048-token prompt in 128-token chunks) group i of the last pass is chunk i.
+runs in start order -- under a driver that forwards a prompt in equal chunks, one launch sequence per chunk, group i of the last pass is chunk i.
 usage: prof_by_chunk.py results.db substring[,substring...] [calls_per_group=32] [last_n_groups=16] [--mod N]
 --mod N: instead of groups, average the calls by (call index % N) (e.g. 3: the QKV / O / down launches of gemm4k_kernel<0>)"""
 import sqlite3, sys
