@@ -316,16 +316,16 @@ const char *ps_hip_last_matmul_kernel(void);
  * replay it names what the capture enqueued. */
 const char *ps_hip_last_attention_kernel(void);
 int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_words);
-/* Diagnostic: tunables of the library (process-wide).  (Keys 1 and 2 selected wave configurations of the decode mat-vec that are no longer compiled: unknown keys now.)
+/* Diagnostic: tunables of the library (process-wide).  (Keys 1 and 2 selected wave configurations of the decode mat-vec that are no longer compiled, key 6 the column blocks per XCD of the wide Q4_K / Q5_K
+ * mat-mul's item order, a constant now (k_gemm4k.hip G4K_CBX): unknown keys.)
  * key 3: the narrow-batch Q4_K mat-mul for few row tiles (k_gemm4k.hip: 0 = gemm4k_par_kernel off (the wave-per-tile / staged forms take the launch: A/B only),
  * 4 / 8 = gemm4k_par_kernel with that many waves per tile, 1 = by tile count, the default); key 4: the fp16 perf mode's GEMM (perf16.hip:
  * 0 = by shape, 1 = 128-token tiles, 2 = 256 x 256 tiles); key 5: the next `value` single-token forwards on the one-launch attention
  * report a time-out of its score exchange (tests of the retry paths: forward, forward_tree, prefill tail, decode_greedy, lowered forward +
- * kv_advance); key 6: column blocks per XCD of the wide Q4_K / Q5_K mat-mul's item order (k_gemm4k.hip g4k_item: 0 = round 2's order, default 4;
- * PS_G4K_CBX); key 7: 1 = the fused Q / K / V + attention launch (k_qkvattn.hip) wherever it is covered -- by default only where its grid fills three quarters
+ * kv_advance); key 7: 1 = the fused Q / K / V + attention launch (k_qkvattn.hip) wherever it is covered -- by default only where its grid fills three quarters
  * of the chip (head size 128 with 8 kv heads), the head-size-64 instance otherwise runs under test only; key 9: the single-token attention kernels read the cached K rows / V channels
- * with plain (0) or non-temporal (1) loads whatever the cache's size, -1 (default): by the rule of csrc/model.hip (a cache-policy hint: no result bit depends on it; PS_KV_STREAM); key 10: F16 batches on the matrix cores (0, default) or on the VALU chain kernel (1: A/B only, same bits);
- * key 11: the fused launch's first rendezvous on tagged granules (0, default) or on the counter (1: A/B and fallback; PS_QA_COUNTER).
+ * with plain (0) or non-temporal (1) loads whatever the cache's size, -1 (default): by the rule of csrc/model.hip (a cache-policy hint: no result bit depends on it); key 10: F16 batches on the matrix cores (0, default) or on the VALU chain kernel (1: A/B only, same bits);
+ * key 11: the fused launch's first rendezvous on tagged granules (0, default) or on the counter (1: A/B and fallback).
  * Returns non-zero for an unknown key.  (A captured single-token step keeps the launch plan it was captured with: ps_hip_model_set_mode drops it.) */
 int ps_hip_debug_set(int key, int value);
 /* Diagnostic: one GEMM shape of the fp16 perf mode on synthetic operands (tools/f16_gemm_bench.py): out[M][N] = x[M][K] . W[N][K]^T, timed over

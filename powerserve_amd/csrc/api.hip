@@ -460,6 +460,32 @@ void psk_note_attn(const char *fmt, ...) {
     vsnprintf(g_last_attn, sizeof(g_last_attn), fmt, ap);
     va_end(ap);
 }
+
+// The timeline buffer (ps_hip_debug_timeline; -DPS_TIMELINE=1 builds): gemv4, gemm4k and the attention kernels record into the slot their launcher
+// gets from psk_gemv_dbg_buf.  Two halves of TIMELINE_WGS workgroup slots, 64 words each.
+static constexpr int TIMELINE_WGS = 1024; // workgroups with a timeline slot
+static unsigned long long *g_dbg_buf = nullptr;
+static int g_dbg_key = -1;
+
+int psk_gemv_debug(int key, uint64_t *host_out, int n_words) {
+    if (!host_out) {
+        if (key >= 0 && !g_dbg_buf && hipMalloc((void **)&g_dbg_buf, (size_t)2 * TIMELINE_WGS * 64 * 8) != hipSuccess) return 2;
+        if (key >= 0 && hipMemset(g_dbg_buf, 0, (size_t)2 * TIMELINE_WGS * 64 * 8) != hipSuccess) return 2;
+        g_dbg_key = key;
+        return 0;
+    }
+    if (!g_dbg_buf || n_words > 2 * TIMELINE_WGS * 64) return 1;
+    return hipMemcpy(host_out, g_dbg_buf, (size_t)n_words * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
+}
+
+unsigned long long *psk_gemv_dbg_buf(int epi, int pro) { // key = k1 + 100 * (k2 + 1): launches matching k1 record into the first half, k2 into the second
+    if (!g_dbg_buf || g_dbg_key < 0) return nullptr;
+    const int k1 = g_dbg_key % 100, k2 = g_dbg_key / 100 - 1;
+    if (k1 == epi * 4 + pro) return g_dbg_buf;
+    if (k2 == epi * 4 + pro) return g_dbg_buf + (size_t)TIMELINE_WGS * 64;
+    return nullptr;
+}
+
 extern "C" {
 const char *ps_hip_last_matmul_kernel(void) { return psk_last_kernel(); }
 const char *ps_hip_last_attention_kernel(void) { return g_last_attn; }
@@ -472,12 +498,11 @@ int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_wo
 }
 
 int ps_hip_debug_set(int key, int value) {
-    extern int g_g4k_par, g_f16_variant, g_force_attn_timeout, g_g4k_cbx, g_qa_force, g_kv_stream_force, g_f16_batch, g_qa_counter;
-    // (keys 1 and 2, the mat-vec's wave configuration and a what-if word, left with the configurations they selected: unknown keys now; there never was a key 8)
+    extern int g_g4k_par, g_f16_variant, g_force_attn_timeout, g_qa_force, g_kv_stream_force, g_f16_batch, g_qa_counter;
+    // (keys 1 and 2, the mat-vec's wave configuration and a what-if word, left with the configurations they selected, key 6 with the A/B of the wide mat-mul's item order: unknown keys now; there never was a key 8)
     if (key == 3) { g_g4k_par = value; return 0; } // the narrow-batch Q4_K mat-mul for few row tiles: 0 gemm4k_par_kernel off (A/B), 4 / 8 waves per tile, 1 by tile count (default)
     if (key == 4) { g_f16_variant = value; return 0; } // the fp16 perf mode's GEMM: 0 by shape, 1 / 2 one tile form
     if (key == 5) { g_force_attn_timeout = value; return 0; } // the next `value` one-launch attentions report a time-out (tests of the retry paths)
-    if (key == 6) { g_g4k_cbx = value; return 0; } // column blocks per XCD of the wide mat-mul's item order
     if (key == 7) { g_qa_force = value; return 0; } // the fused QKV + attention launch wherever it is covered (default: only where its grid fills 3/4 of the chip)
     if (key == 9) { g_kv_stream_force = value; return 0; } // single-token attention: the cached K / V with plain (0) / non-temporal (1) loads whatever the cache's size; -1: by size (model.hip)
     if (key == 10) { g_f16_batch = value; return 0; } // F16 batches: 0 matrix cores (default), 1 VALU chains (A/B)

@@ -963,8 +963,8 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm6k_kernel(const G6
 
 } // namespace
 
-int g_g4k_cbx = getenv("PS_G4K_CBX") ? atoi(getenv("PS_G4K_CBX")) : 4; // ps_hip_debug_set(6, v): column blocks per XCD of the wide Q4_K / Q5_K mat-mul's item order (0: round 2's; default 4: profiles/r05_g4k_item_order.txt)
-int g_g4k_par = getenv("PS_GEMM4K_PAR") ? atoi(getenv("PS_GEMM4K_PAR")) : 1; // ps_hip_debug_set(3, v): the few-tile narrow-batch form (gemm4k_par_kernel)
+constexpr int G4K_CBX = 4; // column blocks per XCD of the wide Q4_K / Q5_K mat-mul's item order (profiles/r05_g4k_item_order.txt)
+int g_g4k_par = 1; // ps_hip_debug_set(3, v): the few-tile narrow-batch form (gemm4k_par_kernel)
 // grid, persistence and the wide / narrow choice for a filled-in G4KParams (tasks, pointers, wt)
 // ---- narrow batches, wave-autonomous form (round 3): at most 16 columns, Q4_K.  The producer / consumer kernels above pay a
 // fixed ~0.45 us per super-block step (barriers, LDS round trips) whatever the width, and a K walk is sequential: 12 columns cost
@@ -1389,8 +1389,7 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
     // arithmetic, needs more than the 168 registers of a twelve-wave workgroup: 30 spills, 12.2 k tok/s.)
     // 8B tree forward, ms by width (profiles/r02_tree_forward_latency_8b.json): 2: 4.7, 8: 4.7, 12: 4.8, 16: 4.8 (narrow kernel),
     // 32: 5.9, 64: 6.3, 128: 8.4 (wide); the round-1 kernels that spread a row group's integer work over producer waves
-    // (gemm8): 2: 4.9, 8: 5.0, 12: 6.1, 16: 6.2, 32: 8.8, 64: 12.8, 96: 19.9.  PS_GEMM4K_MIN_COLS moves the switch (default 2, psk_gemm4k_frag).
-    static const bool no_wav = getenv("PS_NO_GEMM4K_WAV") != nullptr; // (A/B switch for measurements)
+    // (gemm8): 2: 4.9, 8: 5.0, 12: 6.1, 16: 6.2, 32: 8.8, 64: 12.8, 96: 19.9.  These kernels take batches from PS_G4K_MIN_COLS columns on (psk_gemm4k_frag).
     const int par_cfg = g_g4k_par; // 0: off, 4 / 8: that many waves per tile, else by tile count
     const int ctw = n_ct <= 1 ? 1 : 4; // column tiles per workgroup: the narrow kernel for at most 16 columns (its two-tile form, CT = 2, spills: 13.7 ms per 8B forward against 5.9 ms, not instantiated)
     p.n_cb = (n_ct + ctw - 1) / ctw;
@@ -1401,11 +1400,8 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
     if (n_cu > 0 && n_wg > n_cu && n_cu % (8 * p.n_cb) == 0) n_wg = n_cu;
     // the XCD-aware item order (g4k_item): column blocks per XCD; only where its arithmetic holds, else the round-2 order
     p.cbx = 0;
-    if (g_g4k_cbx > 0 && n_wg == 256 && p.n_items % 256 == 0 && (p.n_cb & (p.n_cb - 1)) == 0 && p.n_cb <= 8) {
-        int cbx = g_g4k_cbx < p.n_cb ? g_g4k_cbx : p.n_cb;
-        while (cbx & (cbx - 1)) cbx &= cbx - 1; // a power of two
-        if (cbx < p.n_cb) p.cbx = cbx;          // (cbx == n_cb IS the round-2 order)
-    }
+    static_assert(G4K_CBX > 0 && (G4K_CBX & (G4K_CBX - 1)) == 0, "a power of two");
+    if (n_wg == 256 && p.n_items % 256 == 0 && (p.n_cb & (p.n_cb - 1)) == 0 && p.n_cb <= 8 && G4K_CBX < p.n_cb) p.cbx = G4K_CBX; // (cbx == n_cb IS the round-2 order)
     const dim3 grid((unsigned)n_wg), blk((G4K_NC + G4K_NP) * 64), blkn((G4K_NC + G4K_NPN) * 64);
     static_assert(G4K_RING == 4, "nsb % 4 == 0 is what the producers' ring is unrolled for");
     constexpr int LDS1 = G4K_XCH + 8 * 64 * 8 * 2 * 4 + PS_EXP2F_N * 8;
@@ -1421,7 +1417,7 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
     if (p.wt == PS_Q5_K) { // (single matrix, EPI 0)
         if (ctw == 1) { psk_note_kernel("gemm4k_narrow_kernel<0, 1, 13>"); hipLaunchKernelGGL((gemm4k_narrow_kernel<0, 1, PS_Q5_K>), grid, blkn, LDS1, st, p); }
         else { psk_note_kernel("gemm4k_kernel<0, 13>"); hipLaunchKernelGGL((gemm4k_kernel<0, PS_Q5_K>), grid, blk, G4K_LDS, st, p); }
-    } else if (ctw == 1 && n_ct == 1 && !no_wav && epi != 1 && par_cfg != 0 && 2 * p.n_tasks < 4 * n_cu) {
+    } else if (ctw == 1 && n_ct == 1 && epi != 1 && par_cfg != 0 && 2 * p.n_tasks < 4 * n_cu) {
         // at most 16 columns, few row tiles (Q / K / V, O, down of a tree batch): the super-blocks of a round side by side, the chains behind them
         // (any nsb).  8B, 12 wide, us per launch, four waves walking K -> this: see profiles/r04_tree12_kernel_stats.txt
         static unsigned long long attrp = 0;
@@ -1432,7 +1428,7 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
         const int nwv = par_cfg == 4 || par_cfg == 8 ? par_cfg : (2 * p.n_tasks > n_cu ? 4 : 8); // more tiles than CUs: two workgroups of four waves per CU
         if (nwv == 8) { psk_note_kernel("gemm4k_par_kernel<8>"); hipLaunchKernelGGL((gemm4k_par_kernel<8>), dim3((unsigned)(2 * p.n_tasks)), dim3(512), g4k_par_lds(8), st, p); }
         else { psk_note_kernel("gemm4k_par_kernel<4>"); hipLaunchKernelGGL((gemm4k_par_kernel<4>), dim3((unsigned)(2 * p.n_tasks)), dim3(256), g4k_par_lds(4), st, p); }
-    } else if (ctw == 1 && n_ct == 1 && !no_wav && p.nsb % 8 == 0) { // at most 16 columns: the wave-autonomous form
+    } else if (ctw == 1 && n_ct == 1 && p.nsb % 8 == 0) { // at most 16 columns: the wave-autonomous form
         // 8B tree forward 12 wide, us per launch, staged narrow kernel -> these (profiles/r03_tree12_kernel_stats*.txt): gate / up 39.6 -> 23.6,
         // Q / K / V and O 13 -> 11, down 31 -> 31, lm_head 151 -> 88; the forward 4.59 -> 3.68 ms.  Measured and not kept: the accumulator
         // lanes of a tile split over four unsynchronised waves with dword loads (every 128-byte line fetched from L2 eight times: 46 us
@@ -1441,7 +1437,7 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
         // super-block step whatever was tried on it: its LDS operands fetched a step ahead (16.7 us average per launch, as before), the
         // header operands derived once by the parking wave instead of by all four (170 -> ~110 instructions per step: 16.6 us), a fifth
         // wave that owns the HBM stream with an eight-deep fragment ring in the others (22.9 us).
-        // EPI 0 comes here with many tiles (lm_head: a wave per tile, occupancy hides the latency) and, A/B only, with few tiles under PS_GEMM4K_PAR=0
+        // EPI 0 comes here with many tiles (lm_head: a wave per tile, occupancy hides the latency) and, A/B only, with few tiles under ps_hip_debug_set(3, 0)
         if (epi == 1) g4k_launch_wav<1, 2, 2>(st, p);
         else g4k_launch_wav<0, 2, 2>(st, p);
     } else if (ctw == 1) {
@@ -1455,8 +1451,7 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
 // Q4_K batched mat-mul from fragment-major Q8_K activations (act.qf).  With a.rope (a Q / K / V batch of at most 16 columns: the narrow
 // kernel) the epilogue rotates and appends to the KV cache: 8B tree forward 12 wide 4.72 -> 4.62 ms.
 bool psk_gemm4k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
-    static const bool off = getenv("PS_NO_GEMM4K") != nullptr; // (A/B switch for measurements)
-    if (off || a.pro != 0 || a.n_w < 1 || !psk_gemm4k_frag(K, bs)) return false;
+    if (a.pro != 0 || a.n_w < 1 || !psk_gemm4k_frag(K, bs)) return false;
     if (a.rope && (a.n_w != 3 || a.silu_pair || a.residual || bs > 16)) return false;
     for (int i = 0; i < a.n_w; i++)
         if (a.w[i]->dtype != PS_Q4_K || a.w[i]->K != K || a.w[i]->N % 32 || a.ldo[i] % 4) return false;
@@ -1481,9 +1476,8 @@ int psk_gemm4k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int
 
 // Q5_K (single matrix, the Q5_K_M mix): the same kernels with the Q5_K producer.
 bool psk_gemm5k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
-    static const bool off = getenv("PS_NO_GEMM5K") != nullptr; // (A/B switch for measurements)
     const ps_weight *w = a.w[0];
-    return !off && a.n_w == 1 && !a.silu_pair && w->dtype == PS_Q5_K && w->K == K && w->N % 32 == 0 && a.ldo[0] % 4 == 0 && psk_gemm4k_frag(K, bs);
+    return a.n_w == 1 && !a.silu_pair && w->dtype == PS_Q5_K && w->K == K && w->N % 32 == 0 && a.ldo[0] % 4 == 0 && psk_gemm4k_frag(K, bs);
 }
 int psk_gemm5k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
     const ps_weight *w = a.w[0];
@@ -1496,10 +1490,9 @@ int psk_gemm5k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int
 
 // Q6_K batched mat-mul from the same fragment-major activations (narrower batches keep the 8-column mat-vec launches).
 bool psk_gemm6k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
-    static const bool off = getenv("PS_NO_GEMM6K") != nullptr; // (A/B switch for measurements)
-    static const int64_t min_cols = [] { const char *e = getenv("PS_GEMM6K_MIN_COLS"); return e ? (int64_t)atoll(e) : (int64_t)9; }(); // (8B Q4_K_M tree forward, ms, threshold 17 / 9 / 2: 8 wide 5.9 / 6.0 / 6.2, 12: 6.9 / 6.3 / 6.3, 16: 7.6 / 6.4 / 6.3)
+    constexpr int64_t min_cols = 9; // (8B Q4_K_M tree forward, ms, threshold 17 / 9 / 2: 8 wide 5.9 / 6.0 / 6.2, 12: 6.9 / 6.3 / 6.3, 16: 7.6 / 6.4 / 6.3)
     const ps_weight *w = a.w[0];
-    return !off && a.n_w == 1 && !a.silu_pair && w->dtype == PS_Q6_K && w->K == K && w->N % 32 == 0 && a.ldo[0] % 2 == 0 && bs >= min_cols && psk_gemm4k_frag(K, bs);
+    return a.n_w == 1 && !a.silu_pair && w->dtype == PS_Q6_K && w->K == K && w->N % 32 == 0 && a.ldo[0] % 2 == 0 && bs >= min_cols && psk_gemm4k_frag(K, bs);
 }
 int psk_gemm6k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
     const ps_weight *w = a.w[0];

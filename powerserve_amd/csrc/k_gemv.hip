@@ -20,6 +20,10 @@
 //   * the activation row is quantized ONCE PER WORKGROUP in the prologue (RMSNorm / plain / pre-quantized),
 //     bit-exactly (ps_quant_dev.h), into LDS; it is re-read per unit with ds_read_b32 broadcast across rows.
 //   * up to three matrices share a launch (QKV, gate+up) and the epilogue applies bias / residual / SiLU*up.
+//
+// These are the fallback kernels: gemv4 / gemvb / gemvk take the single columns of the decode path and gemm4k the Q4_K batches.  Which shapes
+// still end here, by kernel family and template instance, is the table "What still reaches k_gemv.hip" in DESIGN.md 5; tests/test_gpu_ops.py
+// (test_mul_mat_fallback_routes) runs one shape per row of it.  Only the instances of that table are compiled.
 #include "ps_gemv_dev.h"
 
 namespace {
@@ -44,15 +48,16 @@ struct GemvParams {
     const int8_t *aq;
     const float *ad;
     const int16_t *abs16;
-    unsigned long long *dbg; // timeline buffer or null (ps_hip_debug_timeline)
 };
 
 // EPI 0: out = y (+bias) (+residual).   EPI 1: out[0] = silu(y_w0) * y_w1 (same row of w[0] and w[1]).
 // NWV waves per workgroup share one LDS copy of the BS activation columns; a wave owns a row group at a time and
-// keeps the fma chains of all BS columns in its own registers (no exchange).  BS 1/4 with 4 waves: small batches;
-// BS 8/16 with 16 waves: prefill / tree-verify column groups from pre-quantized activations (PRO 0).
+// keeps the fma chains of all BS columns in its own registers (no exchange).  BS 1: single columns of rows longer than 64 units, any prologue;
+// BS 4: the column groups of a batch that gemm4k / gemm8 decline, always from pre-quantized activations (PRO 0: matmul.hip lane_major).
 template <int WT, int BS, int EPI, int PRO, int NWV>
 __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const GemvParams p) {
+    static_assert(NWV == 4 && (BS == 1 || (BS == 4 && PRO == 0)) && !(EPI == 1 && PRO == 2),
+                  "the instances dispatch reaches (DESIGN.md 5; the parameters keep their places for the instance names of the profile records)");
     constexpr int NT = NWV * 64;
     using TR = WTraits<WT>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -418,21 +423,11 @@ void launch_g1_ep(hipStream_t st, int n_cu, const GemvParams &p, int epi, int pr
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// (The first producer / consumer decode kernel, gemv3 -- 14 producer waves + 2 chain waves per 1024-thread workgroup, integer
-//  records, the chain waves deriving every block scale -- lived here through round 2.  Every shape it took now goes to its
-//  successors: Q4_K to gemv4 (k_gemv4.hip), Q4_0 / Q8_0 to gemvb (k_gemvb.hip), Q6_K / Q5_K to gemvk (k_gemvk.hip); what they do
-//  not cover -- row lengths that are not whole units of four, very short rows, the long single-matrix stream of a Q4_0 / Q8_0
-//  lm_head -- was never gemv3's either and takes gemv1 / gemv_kernel below.  Deleted in round 3; DESIGN.md 5 keeps its history.)
-constexpr int G3_DBG_WGS = 1024; // workgroups with a timeline slot (ps_hip_debug_timeline: gemv4, gemm4k, the attention kernels)
-unsigned long long *g_dbg_buf = nullptr;
-int g_dbg_key = -1;
-
 // returns false when the row is too long for the register-resident kernel (falls back to gemv_kernel)
 template <int WT>
 bool launch_g1_wt(hipStream_t st, int n_cu, const GemvParams &p, int epi, int pro) {
     const int unit = WTraits<WT>::UNIT;
     const int n_units = (int)((p.K + unit - 1) / unit), tot = epi == 1 ? 2 * n_units : n_units;
-    if (epi == 1 && pro == 2) return false;
     if (tot <= 8) launch_g1_ep<WT, 2, 4>(st, n_cu, p, epi, pro);
     else if (tot <= 16) launch_g1_ep<WT, 4, 4>(st, n_cu, p, epi, pro);
     else if (tot <= 32) launch_g1_ep<WT, 4, 8>(st, n_cu, p, epi, pro);
@@ -446,7 +441,7 @@ void launch_one(hipStream_t st, int n_cu, const GemvParams &p) {
     const int64_t n_tasks = (EPI == 1) ? p.w[0].n_groups : p.groups_total;
     const size_t smem     = (size_t)p.col_bytes * BS;
     int64_t grid          = (n_tasks + NWV - 1) / NWV;
-    const int64_t cap     = (int64_t)n_cu * (NWV == 16 ? 1 : (smem > 40 * 1024 ? 2 : 4));
+    const int64_t cap     = (int64_t)n_cu * (smem > 40 * 1024 ? 2 : 4);
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
     static unsigned long long attr_set = 0; // devices that have the attribute
@@ -457,25 +452,20 @@ void launch_one(hipStream_t st, int n_cu, const GemvParams &p) {
     hipLaunchKernelGGL((gemv_kernel<WT, BS, EPI, PRO, NWV>), dim3((unsigned)grid), dim3(NWV * 64), smem, st, p);
 }
 
-template <int WT, int BS>
-int launch_epi(hipStream_t st, int n_cu, const GemvParams &p, int epi, int pro) {
-    if (epi == 1) {
-        if (pro == 0) launch_one<WT, BS, 1, 0, 4>(st, n_cu, p);
-        else if (pro == 1) launch_one<WT, BS, 1, 1, 4>(st, n_cu, p);
-        else launch_one<WT, BS, 1, 2, 4>(st, n_cu, p);
-    } else {
-        if (pro == 0) launch_one<WT, BS, 0, 0, 4>(st, n_cu, p);
-        else if (pro == 1) launch_one<WT, BS, 0, 1, 4>(st, n_cu, p);
-        else launch_one<WT, BS, 0, 2, 4>(st, n_cu, p);
-    }
-    return 0;
-}
-
+// (psk_gemv_takes: a SiLU pair never comes with the plain quantizer prologue, 2..4 columns always come pre-quantized)
 template <int WT>
 int launch_wt(hipStream_t st, int n_cu, const GemvParams &p, int epi, int pro) {
     if (p.bs == 1 && launch_g1_wt<WT>(st, n_cu, p, epi, pro)) return 0;
-    if (p.bs == 1) return launch_epi<WT, 1>(st, n_cu, p, epi, pro);
-    return launch_epi<WT, 4>(st, n_cu, p, epi, pro);
+    if (p.bs > 1) {
+        if (epi == 1) launch_one<WT, 4, 1, 0, 4>(st, n_cu, p); else launch_one<WT, 4, 0, 0, 4>(st, n_cu, p);
+    } else if (epi == 1) {
+        if (pro == 0) launch_one<WT, 1, 1, 0, 4>(st, n_cu, p); else launch_one<WT, 1, 1, 1, 4>(st, n_cu, p);
+    } else {
+        if (pro == 0) launch_one<WT, 1, 0, 0, 4>(st, n_cu, p);
+        else if (pro == 1) launch_one<WT, 1, 0, 1, 4>(st, n_cu, p);
+        else launch_one<WT, 1, 0, 2, 4>(st, n_cu, p);
+    }
+    return 0;
 }
 
 // Activation image of 8 / 16 pre-quantized columns in LDS, shared by gemm8m_kernel and gemm8b_kernel.
@@ -854,25 +844,6 @@ __global__ __launch_bounds__(NWV * 64) void gemm8b_kernel(const GemvParams p) {
 
 } // namespace
 
-int psk_gemv_debug(int key, uint64_t *host_out, int n_words) {
-    if (!host_out) {
-        if (key >= 0 && !g_dbg_buf && hipMalloc((void **)&g_dbg_buf, (size_t)2 * G3_DBG_WGS * 64 * 8) != hipSuccess) return 2;
-        if (key >= 0 && hipMemset(g_dbg_buf, 0, (size_t)2 * G3_DBG_WGS * 64 * 8) != hipSuccess) return 2;
-        g_dbg_key = key;
-        return 0;
-    }
-    if (!g_dbg_buf || n_words > 2 * G3_DBG_WGS * 64) return 1;
-    return hipMemcpy(host_out, g_dbg_buf, (size_t)n_words * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
-}
-
-unsigned long long *psk_gemv_dbg_buf(int epi, int pro) { // key = k1 + 100 * (k2 + 1): launches matching k1 record into the first half, k2 into the second
-    if (!g_dbg_buf || g_dbg_key < 0) return nullptr;
-    const int k1 = g_dbg_key % 100, k2 = g_dbg_key / 100 - 1;
-    if (k1 == epi * 4 + pro) return g_dbg_buf;
-    if (k2 == epi * 4 + pro) return g_dbg_buf + (size_t)G3_DBG_WGS * 64;
-    return nullptr;
-}
-
 size_t psk_gemv_lds_col_bytes(int wt, int64_t K) {
     const int64_t blk = (wt == PS_Q4_K) ? 256 : 32, unit = (wt == PS_Q4_K) ? 256 : 128;
     const int64_t Kp = (K + unit - 1) / unit * unit;
@@ -897,9 +868,12 @@ static void launch_gemm8b_k(hipStream_t st, const GemvParams &p, const dim3 grid
 }
 template <int WT>
 static int launch_gemm8(hipStream_t st, const GemvParams &p, int epi, int nwv, const dim3 grid, size_t smem) {
-    if constexpr (WT != PS_Q4_K) { // quad dots on the matrix cores
-        if (nwv == 8) launch_gemm8b_k<WT, 1, 8>(st, p, grid, smem); // (Q4_0 gate/up: see psk_gemm8)
-        else if (nwv == 16) { if (epi) launch_gemm8b_k<WT, 1, 16>(st, p, grid, smem); else launch_gemm8b_k<WT, 0, 16>(st, p, grid, smem); }
+    if constexpr (WT == PS_Q4_0) { // quad dots on the matrix cores
+        if (nwv == 8) launch_gemm8b_k<WT, 1, 8>(st, p, grid, smem); // (gate/up, in place of 16 waves: see psk_gemm8)
+        else if (nwv == 16) launch_gemm8b_k<WT, 0, 16>(st, p, grid, smem);
+        else { if (epi) launch_gemm8b_k<WT, 1, 4>(st, p, grid, smem); else launch_gemm8b_k<WT, 0, 4>(st, p, grid, smem); }
+    } else if constexpr (WT == PS_Q8_0) {
+        if (nwv == 16) { if (epi) launch_gemm8b_k<WT, 1, 16>(st, p, grid, smem); else launch_gemm8b_k<WT, 0, 16>(st, p, grid, smem); }
         else { if (epi) launch_gemm8b_k<WT, 1, 4>(st, p, grid, smem); else launch_gemm8b_k<WT, 0, 4>(st, p, grid, smem); }
     } else {
         if (nwv == 8) { if (epi) launch_gemm8m_k<1, 8, 16>(st, p, grid, smem); else launch_gemm8m_k<0, 8, 16>(st, p, grid, smem); } // 16 columns
@@ -939,8 +913,7 @@ int psk_gemm8(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int6
     size_t smem_l = smem;
     // Q4_K, short rows, wide batches: 16 columns per workgroup of 8 waves (the weight-side work of a unit is shared by
     // twice the columns; the image of 16 columns has to fit the LDS)
-    static const bool no16 = getenv("PS_GEMM8_C8") != nullptr;
-    if (wt == PS_Q4_K && !no16 && nwv == 16 && bs > 8 && 2 * smem <= 80 * 1024) { nwv = 8; ncg = (bs + 15) / 16; smem_l = 2 * smem; }
+    if (wt == PS_Q4_K && nwv == 16 && bs > 8 && 2 * smem <= 80 * 1024) { nwv = 8; ncg = (bs + 15) / 16; smem_l = 2 * smem; }
     if (wt == PS_Q4_0 && epi == 1 && nwv == 16) nwv = 8; // two column sets + the held gate rows need more than the 128 VGPRs of a 16-wave workgroup
     const dim3 grid((unsigned)((n_tasks + nwv - 1) / nwv), (unsigned)ncg);
     switch (wt) {
@@ -950,10 +923,11 @@ int psk_gemm8(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int6
     }
 }
 
-// 1..4 columns per launch (the 8-column instantiations of the in-lane kernel measured slower than 4; batches take psk_gemm8): the
-// single-column shapes that gemv4 / gemvb do not take, and the column groups of a batch that the batched mat-muls decline
+// 1..4 columns per launch: the single-column shapes that gemv4 / gemvb do not take, and the column groups of a batch that the batched
+// mat-muls decline -- those come pre-quantized (matmul.hip lane_major).  The routes, one by one: DESIGN.md 5.
 bool psk_gemv_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
     if (bs < 1 || bs > 4 || a.n_w < 1 || a.n_w > 3 || a.rope) return false;
+    if ((bs > 1 && a.pro != 0) || (a.silu_pair && a.pro == 2)) return false; // (no caller asks for them: not instantiated)
     const int wt = a.w[0]->dtype;
     if (wt != PS_Q4_0 && wt != PS_Q8_0 && wt != PS_Q4_K) return false;
     for (int i = 0; i < a.n_w; i++)

@@ -413,8 +413,7 @@ int launch_g4_kc(hipStream_t st, int grid, const G4Params &p, int epi, int pro) 
 } // namespace
 
 bool psk_gemv4_takes(const psk_gemv_args &a, int64_t K, int64_t bs) { // rows end on multiples of four units
-    static const bool off = getenv("PS_NO_GEMV4") != nullptr; // (A/B switch for measurements)
-    if (off || bs != 1 || a.n_w < 1 || a.n_w > 3 || K % 1024 || K > 16384) return false;
+    if (bs != 1 || a.n_w < 1 || a.n_w > 3 || K % 1024 || K > 16384) return false;
     for (int i = 0; i < a.n_w; i++)
         if (a.w[i]->dtype != PS_Q4_K || a.w[i]->K != K || a.w[i]->N < 1) return false;
     if (a.silu_pair) return a.n_w == 2 && a.w[0]->N == a.w[1]->N && a.pro != 2; // (the SiLU pair has no plain-quantizer prologue)

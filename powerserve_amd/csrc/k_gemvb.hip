@@ -405,8 +405,7 @@ static int gb_tasks(const psk_gemv_args &a) { // row groups (a SiLU pair: of w[0
 // workgroup, gemv1's 256-thread workgroups start faster) and the long single-matrix stream of the lm_head (1B 40.5 / 37.8,
 // 0.5B 48 / 41: the one LDS pipe of a workgroup carries three record float4s per unit both ways) go to gemv1.
 bool psk_gemvb_takes(const psk_gemv_args &a, int64_t K, int64_t bs, int n_cu) {
-    static const bool off = getenv("PS_NO_GEMVB") != nullptr; // (A/B switch for measurements)
-    if (off || bs != 1 || a.n_w < 1 || a.n_w > 3) return false;
+    if (bs != 1 || a.n_w < 1 || a.n_w > 3) return false;
     const int wt = a.w[0]->dtype;
     if ((wt != PS_Q4_0 && wt != PS_Q8_0) || K < 128 || K % 128 || K > 16384) return false;
     for (int i = 0; i < a.n_w; i++)

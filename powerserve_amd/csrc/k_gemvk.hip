@@ -431,8 +431,7 @@ int launch_gk_wt(hipStream_t st, int grid, const GKParams &p, int epi, int pro) 
 // Single-column Q6_K / Q5_K mat-vec; all matrices of one type.  (Pre-quantized single columns do not occur on the decode path: PRO 0 is not
 // instantiated, those columns take a quantizer launch + k_gemv6.hip.)
 bool psk_gemvk_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
-    static const bool off = getenv("PS_NO_GEMVK") != nullptr; // (A/B switch for measurements)
-    if (off || bs != 1 || a.n_w < 1 || a.n_w > 3 || a.pro == 0) return false;
+    if (bs != 1 || a.n_w < 1 || a.n_w > 3 || a.pro == 0) return false;
     const int wt = a.w[0]->dtype;
     if ((wt != PS_Q6_K && wt != PS_Q5_K) || K < 256 || K % 256 || K > 16384) return false;
     for (int i = 0; i < a.n_w; i++)

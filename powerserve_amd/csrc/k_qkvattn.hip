@@ -649,12 +649,10 @@ size_t qa_lds_bytes(const QAParams &p, int hs) {
 } // namespace
 
 int g_qa_force = 0; // ps_hip_debug_set(7, v)
-int g_qa_counter = getenv("PS_QA_COUNTER") ? atoi(getenv("PS_QA_COUNTER")) : 0; // ps_hip_debug_set(11, v): 1 = rendezvous A on the counter (round 6's hand-off) instead of granules
+int g_qa_counter = 0; // ps_hip_debug_set(11, v): 1 = rendezvous A on the counter (round 6's hand-off) instead of granules
 
 // Q / K / V mat-vec (RMSNorm + quantizer prologue, RoPE + KV append) + single-token attention in ONE launch.  false: not covered -- the caller issues the two launches.
 bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, const psl_attn_args &a) {
-    static const bool off = getenv("PS_NO_QKV_ATTN") != nullptr; // (A/B switch for measurements)
-    if (off) return false;
     const int hs = a.head_size, r2 = a.n_heads / a.n_kv_heads, G = hs / 4;
     if (g.n_w != 3 || !g.rope || g.rope_wi0 != 0 || g.pro != 1 || g.silu_pair || g.residual) return false;
     for (int i = 0; i < 3; i++) if (g.w[i]->dtype != PS_Q4_K || g.w[i]->K != K) return false;
@@ -674,7 +672,7 @@ bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, c
     const psk_rope_kv &rk = *g.rope;
     if (g.out[0] != a.q || rk.rope_table != a.rope_table || rk.rope_pos || rk.k_cache != a.k_cache || rk.v_cache != a.v_cache || rk.head_size != hs ||
         rk.n_dims != a.n_dims || rk.n_ctx != a.n_ctx || rk.kv_dim != a.n_kv_heads * hs || rk.state != a.state || rk.k16 || rk.v16) return false;
-    if (!psk_gemv4_takes(g, K, 1)) return false; // (its mat-vec half is gemv4's: PS_NO_GEMV4 switches it off too)
+    if (!psk_gemv4_takes(g, K, 1)) return false; // (its mat-vec half is gemv4's)
     // The launch has head_size / 4 workgroups per kv head: 256 for Llama-3.1-8B's shape, 128 for Llama-3.2-1B's (head size 64) -- half the chip for a mat-vec that the
     // unfused launch spreads over every CU: measured slower there (tools/gpu_fused_stress.py, profiles/r06_fused_stress.txt: 11.9 k vs 12.4 k tok/s on the 2-layer
     // 1B shape in Q4_K, against 4.84 k vs 4.77 k on the 4-layer 8B shape).  Taken only where its grid fills at least three quarters of the chip;

@@ -188,8 +188,7 @@ void psk_quantize_act(hipStream_t st, int vdt, int mode, const float *x, const f
     if (mode == 1) {
         dim3 g((unsigned)rows), b(256);
         const int64_t tpw = ((K + 255) / 256 + 3) / 4;
-        static const bool wide_off = getenv("PS_NO_QNORM_WIDE") != nullptr;
-        if (!wide_off && rows >= 2 && K % 256 == 0 && K / 256 >= 8 && K / 256 <= 16) { // batches: one wave per tile
+        if (rows >= 2 && K % 256 == 0 && K / 256 >= 8 && K / 256 <= 16) { // batches: one wave per tile
             dim3 bw((unsigned)(K / 256 * 64));
             if (vdt == PS_Q8_0) hipLaunchKernelGGL((quantize_norm_wide_kernel<PS_Q8_0>), g, bw, 0, st, a);
             else hipLaunchKernelGGL((quantize_norm_wide_kernel<PS_Q8_K>), g, bw, 0, st, a);

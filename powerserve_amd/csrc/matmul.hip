@@ -1,7 +1,7 @@
 // The quantized / F16 mat-mul dispatcher (host code): which launch(es) run a group of matrices that share an activation, for the model,
 // the op API (ps_hip_mul_mat) and the plans that must know it in advance (psk_matmul_fuses_rope) -- one chain, walked to enqueue or to plan:
 //   F16 group: gemvh.  Single column, all Q6_K / Q5_K: gemvk.  Mixed types or Q6_K / Q5_K: each(), a launch per run of a type.
-//   One lane-major type (Q4_K / Q4_0 / Q8_0): from gemm_min_bs() columns on, the activation quantized once and gemm4k, else gemm8;
+//   One lane-major type (Q4_K / Q4_0 / Q8_0): from GEMM_MIN_BS columns on, the activation quantized once and gemm4k, else gemm8;
 //   what they decline in column groups of 4 (one column: gemv4, gemvb, else gemv).
 #include "ps_internal.h"
 #include "ps_ops.h"
@@ -10,10 +10,7 @@ namespace {
 
 // from this many columns on a launch quantizes its activation ONCE into `act` and goes to the batched kernels (2-4 columns: 4.8-4.9 ms
 // per 8B forward through the batched kernel, 5.4-6.3 ms through the 4-column mat-vec)
-int gemm_min_bs() {
-    static const int v = getenv("PS_GEMM8_MIN_BS") ? atoi(getenv("PS_GEMM8_MIN_BS")) : 2;
-    return v;
-}
+constexpr int GEMM_MIN_BS = 2;
 
 // One walk of the chain.  s == nullptr: a plan -- the rungs are chosen as for the real thing, nothing is enqueued.
 struct Mm {
@@ -42,7 +39,7 @@ int lane_major(const Mm &m, const psk_gemv_args &g, bool *q8k) {
     const int64_t blk = vdt == PS_Q8_0 ? 32 : 256;
     const ps_act act = m.s ? m.s->act : ps_act{};
     psk_gemv_args gq = g;
-    if (bs >= gemm_min_bs()) {
+    if (bs >= GEMM_MIN_BS) {
         // batches: the activation is quantized ONCE (with its RMSNorm when the launch carries one) and the weights are
         // streamed once per column group of up to 16 instead of once per 4 columns
         if (g.pro) {
@@ -178,8 +175,7 @@ int psk_matmul(ps_hip_ctx *c, const psk_gemv_args &g, const psk_mm_scratch &s, i
 }
 
 bool psk_matmul_fuses_rope(const ps_hip_ctx *c, const psk_gemv_args &g, int64_t K, int64_t bs) {
-    static const bool off = getenv("PS_NO_ROPE_FUSION") != nullptr; // (batches: the rotation in the chunk mat-mul's epilogue off, for A/B)
-    if (!g.rope || (off && bs > 1)) return false;
+    if (!g.rope) return false;
     // every launch of the chain takes its part of the rotation: a rung without the epilogue is "not covered", so the plan fails
     return matmul(Mm{nullptr, nullptr, c->n_cu, K, bs}, g) == 0;
 }

@@ -235,7 +235,7 @@ static psk_gemv_args mm_args(const ps_hip_model *m, mm_group which, uint32_t L) 
     return g;
 }
 
-int g_kv_stream_force = getenv("PS_KV_STREAM") ? atoi(getenv("PS_KV_STREAM")) : -1; // ps_hip_debug_set(9, v)
+int g_kv_stream_force = -1; // ps_hip_debug_set(9, v)
 // What one forward consists of: everything enqueue_forward is told, by name (nothing is set on the model before a call and cleared after it)
 struct fwd_opts {
     bool lm_head = false;  // final norm + lm_head + arg-max (or the sampler chain)
@@ -283,8 +283,8 @@ static int enqueue_forward(ps_hip_model *m, int bs, const fwd_opts &o) {
     // Single-token attention: are the cached K rows / V channels read with non-temporal loads (psl_attn_args::kv_stream)?  Measured (profiles/r06_kv_stream_threshold.txt,
     // r06_ad2_nt_small_models.txt): the fused Q / K / V + attention launch is faster with them at every cache length tried (8B: +1.0 % behind a 256-token prompt, +1.6 % behind
     // 1024, +2.2 % behind 2048); the attention launch of its own (attn_decode2) gains where the whole cache -- every layer, K and V -- is more than the memory-side cache keeps
-    // from token to token (8B behind 2048 tokens, 537 MB: +0.8 %) and loses where it fits (Llama-3.2-1B behind 512 tokens, 42 MB: -2.2 %).  PS_KV_STREAM=0 / 1 forces both (A/B).
-    const int kvs_force = g_kv_stream_force; // (PS_KV_STREAM / ps_hip_debug_set(9, v): -1 by the rule below, 0 / 1 forced)
+    // from token to token (8B behind 2048 tokens, 537 MB: +0.8 %) and loses where it fits (Llama-3.2-1B behind 512 tokens, 42 MB: -2.2 %).  ps_hip_debug_set(9, 0 / 1) forces both (A/B).
+    const int kvs_force = g_kv_stream_force; // (ps_hip_debug_set(9, v): -1 by the rule below, 0 / 1 forced)
     const int n_kv_now = o.n_kv_host > 0 ? o.n_kv_host : (o.n_kv_hint > 0 ? o.n_kv_hint : (int)kv.position);
     const int kvs_fused = kvs_force >= 0 ? kvs_force : 1;
     const int kvs_own = kvs_force >= 0 ? kvs_force : ((int64_t)f.n_layers * 2 * n_kv_now * kvd * 4 > ((int64_t)160 << 20) ? 1 : 0);

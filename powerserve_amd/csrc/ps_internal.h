@@ -101,13 +101,10 @@ static inline bool ps_first_on_device(unsigned long long *mask) {
     } while (0)
 
 // smallest batch the chunk mat-muls (k_gemm4k.hip) take
-static inline int64_t ps_gemm4k_min_cols() {
-    static const int64_t v = [] { const char *e = getenv("PS_GEMM4K_MIN_COLS"); return e ? (int64_t)atoll(e) : (int64_t)2; }();
-    return v;
-}
+constexpr int64_t PS_G4K_MIN_COLS = 2;
 // the batches whose Q8_K quantization also writes the fragment-major copy (ps_act::qf / mf): every batch that psk_gemm4k_takes,
 // psk_gemm5k_takes or psk_gemm6k_takes can accept
-static inline bool psk_gemm4k_frag(int64_t K, int64_t rows) { return rows >= ps_gemm4k_min_cols() && K % 1024 == 0; }
+static inline bool psk_gemm4k_frag(int64_t K, int64_t rows) { return rows >= PS_G4K_MIN_COLS && K % 1024 == 0; }
 static inline size_t ps_act_bytes(int64_t K, int64_t rows) {
     // qs + d (worst case blk 32) + bs16, each 256-B aligned
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -190,7 +187,7 @@ int psk_matmul(ps_hip_ctx *c, const psk_gemv_args &g, const psk_mm_scratch &s, i
 // will psk_matmul(g) do g.rope's RoPE + KV append in the epilogues of its launches (the model plans the rotation before it enqueues)?
 bool psk_matmul_fuses_rope(const ps_hip_ctx *c, const psk_gemv_args &g, int64_t K, int64_t bs);
 
-// Launcher families.  psk_<family>_takes is the whole condition under which psk_<family> runs `a` (its PS_NO_* switch included); the
+// Launcher families.  psk_<family>_takes is the whole condition under which psk_<family> runs `a`; the
 // dispatcher asks them in order and calls a launcher only after its predicate said yes.  Launchers return 0 or a launch error.
 size_t psk_gemv_lds_col_bytes(int wt, int64_t K);
 // single-column Q4_K mat-vec with the fused prologues / epilogues (k_gemv4.hip)
@@ -230,8 +227,9 @@ static inline int64_t ps_w_unit(int dtype) { return dtype == PS_Q4_K ? 256 : 128
 void psk_f16_act(hipStream_t st, int mode, const float *x, const float *norm_w, float eps, int64_t K, int64_t rows, _Float16 *out);
 bool psk_gemvh_takes(const psk_gemv_args &a, int64_t K, int64_t bs);
 int psk_gemvh(hipStream_t st, int n_cu, const psk_gemv_args &a, _Float16 *x16, int64_t K, int64_t bs);
-int psk_gemv_debug(int key, uint64_t *host_out, int n_words); // timeline buffer: arm / read back
-unsigned long long *psk_gemv_dbg_buf(int epi, int pro); // timeline slot armed for this (epilogue, prologue) pair, or null
+// the timeline buffer of ps_hip_debug_timeline (api.hip): arm / read back, and the slot armed for this (epilogue, prologue) pair, or null
+int psk_gemv_debug(int key, uint64_t *host_out, int n_words);
+unsigned long long *psk_gemv_dbg_buf(int epi, int pro);
 // the template instance the last quantized mat-vec / mat-mul launch of this process used (rocprofv3's kernel name): bench.py's
 // roofline names the kernel that RAN, not the one it expects
 void psk_note_kernel(const char *fmt, ...);

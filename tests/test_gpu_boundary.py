@@ -265,13 +265,14 @@ def test_kv_interface_members(ctx, oracle, tmp_path):
 
 
 def test_removed_debug_keys_are_unknown_and_leave_the_mat_vec_alone(ctx, oracle):
-    """ps_hip_debug_set keys 1 and 2 (the decode mat-vec's wave configuration and a what-if word) left with the kernel configurations they selected:
-    they answer like any unknown key, and nothing of them stays behind -- a Q4_K single column (K = 1024, N = 64: the smallest shape gemv4 takes)
+    """ps_hip_debug_set keys 1 and 2 (the decode mat-vec's wave configuration and a what-if word) left with the kernel configurations they selected,
+    key 6 (the wide mat-mul's column blocks per XCD) became a constant: they answer like any unknown key, and nothing of them stays behind -- a Q4_K single column (K = 1024, N = 64: the smallest shape gemv4 takes)
     still runs gemv4_kernel and is bit-equal to the oracle."""
     from powerserve_amd import synth
     assert ctx.L.ps_hip_debug_set(99, 0) != 0
     assert ctx.L.ps_hip_debug_set(1, 0) != 0
     assert ctx.L.ps_hip_debug_set(2, 0) != 0
+    assert ctx.L.ps_hip_debug_set(6, 4) != 0
     K, N = 1024, 64
     rng = np.random.default_rng(12)
     w = synth.random_blocks(rng, 12, N, K)

@@ -103,6 +103,46 @@ def test_mul_mat_batched(ctx, oracle, hip, wt, K, N, bs):
     W.free()
 
 
+@pytest.mark.parametrize("wt,K,N,bs,kernel", [
+    # gemv1_kernel<WT, UPW, NW, EPI, PRO>: single columns of at most 64 units that gemv4 (K % 1024 != 0) / gemvb (K < 128) decline
+    (12, 256, 64, 1, "gemv1_kernel<12, 2, 4, 0, 2>"),
+    (8, 96, 40, 1, "gemv1_kernel<8, 2, 4, 0, 2>"),
+    (2, 96, 40, 1, "gemv1_kernel<2, 2, 4, 0, 2>"),
+    # gemv_kernel<WT, 1, EPI, PRO, 4>: single columns of more than 64 units (Q4_K: K > 16384; Q4_0 / Q8_0: K % 128 != 0, a partial last unit)
+    (12, 16640, 8, 1, "gemv_kernel<12, 1, 0, 2, 4>"),
+    (8, 8224, 24, 1, "gemv_kernel<8, 1, 0, 2, 4>"),
+    (2, 8224, 24, 1, "gemv_kernel<2, 1, 0, 2, 4>"),
+    # gemv_kernel<WT, 4, EPI, 0, 4>: column groups of a batch, quantized once, that gemm4k and gemm8 decline -- Q4_0 / Q8_0 rows that are not whole
+    # units, Q4_K rows whose 8-column image does not fit the LDS (67 super-blocks) and are not gemm4k's (K % 1024 != 0)
+    (8, 160, 40, 3, "gemv_kernel<8, 4, 0, 0, 4>"),
+    (2, 160, 40, 3, "gemv_kernel<2, 4, 0, 0, 4>"),
+    (12, 17152, 20, 3, "gemv_kernel<12, 4, 0, 0, 4>"),
+    # ... and the single column such a batch ends on (5 = 4 + 1): gemv1_kernel from the pre-quantized activation (PRO 0), after gemv_kernel<WT, 4, ...>
+    (8, 160, 40, 5, "gemv1_kernel<8, 2, 4, 0, 0>"),
+    (2, 160, 40, 5, "gemv1_kernel<2, 2, 4, 0, 0>"),
+    # gemm8m_kernel<EPI, NWV, C> / gemm8b_kernel<WT, EPI, NWV>: batches of whole units that are not gemm4k's (Q4_K with K % 1024 != 0; Q4_0 / Q8_0)
+    (12, 256, 64, 9, "gemm8m_kernel<0, 4, 8>"),
+    (8, 896, 40, 7, "gemm8b_kernel<8, 0, 4>"),
+    (2, 896, 40, 7, "gemm8b_kernel<2, 0, 4>"),
+])
+def test_mul_mat_fallback_routes(ctx, oracle, hip, wt, K, N, bs, kernel):
+    """One shape per row of DESIGN.md 5's table "What still reaches k_gemv.hip", the smallest that takes the route (short rows, a partial
+    row group or last unit where the kernel has the case): bit-equal to the oracle, and the launch went to the kernel family and template
+    instance the table names -- the last launch of the call, for a batch that goes out in column groups."""
+    from powerserve_amd import synth
+    rng = np.random.default_rng(wt * 131 + K + N + bs)
+    w = synth.random_blocks(rng, wt, N, K)
+    x = (rng.standard_normal((bs, K)) * rng.uniform(0.1, 30.0, (bs, 1))).astype(np.float32)
+    want = oracle.mul_mat(wt, w, K, N, x)
+    W = ctx.upload_weight(wt, w, K, N)
+    dx, dy = ctx.to_device(x), ctx.empty((bs, N))
+    ctx.check(ctx.L.ps_hip_mul_mat(ctx.h, C.byref(dy.tensor()), C.byref(W.tensor()), C.byref(dx.tensor())))
+    assert ctx.L.ps_hip_last_matmul_kernel().decode() == kernel
+    got = dy.numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (rel_err(got, want), np.argwhere(got != want)[:8])
+    W.free()
+
+
 @pytest.mark.parametrize("K,N,bs", [(4096, 512, 128), (1024, 96, 120), (14336, 64, 113), (2048, 288, 128), (1024, 64, 160), (2048, 96, 200), (1024, 8224, 70), (1024, 32, 12), (4096, 160, 2), (2048, 8224, 16), (1024, 64, 5)])
 def test_mul_mat_q4k_chunk_on_matrix_cores(ctx, oracle, hip, K, N, bs):
     """Batches of a Q4_K weight from 2 columns (N % 32 == 0, K % 1024 == 0) take k_gemm4k.hip (17 and more: the wide kernel, fewer: the narrow one): fp16 MFMA contractions of

@@ -12,4 +12,4 @@ python tools/prof_summary.py $DB --decode > gpurun_out/r06_decode_kernel_stats_f
 head -8 gpurun_out/r06_decode_kernel_stats_fused.txt
 rm -rf gpurun_out/prof_kt
 timeout 300 python bench.py --steps 32 --warmup 4 2>/dev/null | tail -1 | cut -c1-200 | tee $O/r06_fused_ab.txt
-echo "== two launches"; PS_NO_QKV_ATTN=1 timeout 300 python bench.py --steps 32 --warmup 4 2>/dev/null | tail -1 | cut -c1-200 | tee -a $O/r06_fused_ab.txt
+echo "== two launches (mode bit 7)"; PS_HIP_MODE_OR=128 timeout 300 python bench.py --steps 32 --warmup 4 2>/dev/null | tail -1 | cut -c1-200 | tee -a $O/r06_fused_ab.txt
