@@ -263,6 +263,29 @@ int ps_hip_model_decode_sampled(ps_hip_model *m, int32_t token, int steps, const
 void ps_hip_sample_counters(uint64_t *out2, int reset);
 const char *ps_hip_last_sample_kernels(void);
 
+/* ---- scoring a text on the device: the probability the model gives each target token, as the reference's perplexity tool computes it
+ * (app/perplexity/main.cpp:50-61 over ProbArray::softmax, src/sampler/prob_array.cpp:38-59: max, expf(x - max), a double sum from the
+ * smallest logit to the largest, (float)((double)e_t / sum)), bit for bit (DESIGN.md "Scoring a text on the device").  The device adds in an
+ * order of its own and certifies each row's prob; a row whose certificate does not close is redone on the host with the reference's own
+ * operations (flag bit 0).  log and exp of the perplexity stay with the caller (csrc/host/perplexity.hpp), on the host's libm like the reference's. */
+typedef struct ps_score {
+    float prob;       /* of the row's target; NaN with flag bit 1 or 2 */
+    float max_logit;
+    int32_t argmax;   /* the first maximum, as ps_hip_argmax gives it */
+    uint32_t flags;   /* bit 0: took the exact path; bit 1: the row holds a NaN or a +inf (outside the contract, nothing scored); bit 2: no target */
+} ps_score;
+/* rows of n_vocab logits on the device, row r at logits_dev + r * row_stride (floats; any alignment); targets_host[r] in [-1, n_vocab), -1 = score nothing
+ * (flag bit 2; argmax and max_logit still returned); out_host: rows records.  2 <= n_vocab <= 2^24; anything else is rc 2. */
+int ps_hip_score_rows(ps_hip_ctx *ctx, const float *logits_dev, int n_vocab, int64_t row_stride, int rows, const int32_t *targets_host, ps_score *out_host);
+/* ps_hip_model_prefill(m, tokens, n, chunk) -- same cache rows, same position afterwards, same retry -- that also runs the lm_head for every column and scores
+ * column i against targets[i] (out_host: n records).  The logits are bit-identical to ps_hip_model_forward(chunk tokens, lm_head = 1) called once per chunk
+ * (app/perplexity/main.cpp:113-121); up to max_batch / chunk chunks share a launch sequence as in prefill (in the fp16-KV mode, bit 3, chunks of one token
+ * run one at a time: that mode's attention exists for single-token forwards only).  Refused with rc 2 and nothing advanced: what prefill refuses, a target
+ * outside [-1, vocab), and the fp16 prefill perf mode (bit 5), whose definition excludes batches with logits. */
+int ps_hip_model_score(ps_hip_model *m, const int32_t *tokens, const int32_t *targets, int n, int chunk, ps_score *out_host);
+/* diagnostics: [0] rows scored, [1] of them on the exact path, [2] rows refused for a NaN / +inf, process-wide since the last reset */
+void ps_hip_score_counters(uint64_t *out3, int reset);
+
 /* ---- Sequences: several conversations on one model, decoded together (DESIGN.md "Batched decode").
  * A model holds one or more sequences: a KV cache (K [n_ctx][kv_dim], V [kv_dim][n_ctx] per layer), a position and a visibility table each.  Sequence 0
  * is the cache ps_hip_model_create allocated; a model on which none of these is called behaves exactly as before.  One sequence is the CURRENT one: every
@@ -325,7 +348,8 @@ int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_wo
  * kv_advance); key 7: 1 = the fused Q / K / V + attention launch (k_qkvattn.hip) wherever it is covered -- by default only where its grid fills three quarters
  * of the chip (head size 128 with 8 kv heads), the head-size-64 instance otherwise runs under test only; key 9: the single-token attention kernels read the cached K rows / V channels
  * with plain (0) or non-temporal (1) loads whatever the cache's size, -1 (default): by the rule of csrc/model.hip (a cache-policy hint: no result bit depends on it); key 10: F16 batches on the matrix cores (0, default) or on the VALU chain kernel (1: A/B only, same bits);
- * key 11: the fused launch's first rendezvous on tagged granules (0, default) or on the counter (1: A/B and fallback).
+ * key 11: the fused launch's first rendezvous on tagged granules (0, default) or on the counter (1: A/B and fallback);
+ * key 12: the scoring certificate's eps (csrc/ps_score_dev.h) multiplied by 2^value, 0 <= value <= 100 (default 0; tests and A/B only: eps >= 1 sends every row down the exact path).
  * Returns non-zero for an unknown key.  (A captured single-token step keeps the launch plan it was captured with: ps_hip_model_set_mode drops it.) */
 int ps_hip_debug_set(int key, int value);
 /* Diagnostic: one GEMM shape of the fp16 perf mode on synthetic operands (tools/f16_gemm_bench.py): out[M][N] = x[M][K] . W[N][K]^T, timed over

@@ -75,6 +75,9 @@ struct Model {
     // tokens appended at the cache position.  The first chunk's graph goes through Executor::plan like any forward; when the backend lowers it, the LOOP is
     // lowered too (ps_hip_model_prefill: the same bits, several reference chunks per launch sequence), else every chunk runs through forward().
     void prefill(const std::vector<Token> &tokens, size_t batch_size);
+    // prefill that also scores: tokens appended at the cache position in chunks of batch_size with the lm_head for every column, record i = the probability the
+    // model gives targets[i] behind tokens[0 .. i] (-1: none), bit for bit what the reference's perplexity tool computes (ps_hip_model_score; csrc/host/perplexity.cpp)
+    auto score(const std::vector<Token> &tokens, const std::vector<Token> &targets, size_t batch_size) -> std::vector<ps_score>;
     // ModelTokenIterator: prefill all but the last prompt token in chunks of batch_size (no lm_head), then `steps`
     // single-token greedy steps
     auto generate(const std::vector<Token> &prompt, int steps, size_t batch_size) -> std::vector<Token>;

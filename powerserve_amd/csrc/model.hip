@@ -86,6 +86,9 @@ struct ps_hip_model {
     step_graph graphs[G_COUNT];            // the captured single-token steps (dropped together: drop_graphs)
     ps_sample_dev *sample_dev = nullptr;   // sampler configuration + engine state of the current sampled run (allocated at first use)
     void *sample_scratch = nullptr;
+    void *score_scratch = nullptr;         // scoring (ps_hip_model_score; allocated at first use): k_score.hip's scratch for max_batch rows,
+    int32_t *score_targets = nullptr;      // [max_batch] the targets of the forward's columns,
+    ps_score *score_out = nullptr;         // [max_batch] their records
     uint64_t weight_bytes = 0;
     std::vector<void *> owned;
     // ---- sequences (ps_hip_model_seq_*): the KV state lives here and nowhere else.  Sequence 0 is the cache model_create allocated; the single-sequence
@@ -243,6 +246,7 @@ struct fwd_opts {
     bool rope_pos = false; // RoPE positions from rope_pos_dev (a tree forward)
     bool advance = false;  // with lm_head: the step feeds its own id back and moves the device-side state on (the decode loops)
     bool sampled = false;  // with lm_head: the sampler chain (sample_dev) in place of the arg-max
+    bool score = false;    // with lm_head: every column scored against score_targets (k_score.hip) in place of the arg-max
     // sq: a batched decode step -- column i is a token of ITS OWN sequence (sq->tab); the mat-muls are the column-wise ones of any batch, RoPE + KV append and the
     // attention go per column to that sequence's cache (k_attn.hip, "batched decode")
     const psl_seqs_args *sq = nullptr;
@@ -398,7 +402,8 @@ static int enqueue_forward(ps_hip_model *m, int bs, const fwd_opts &o) {
     if (lm_head) {
         if (mm(m, mm_args(m, MM_LM_HEAD, 0), act_for(dim), dim, bs)) return 2;
         const bool advance = o.advance;
-        if (o.sampled) psl_sample(st, m->logits, (int)f.vocab_size, m->sample_dev, m->sample_scratch, nullptr, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
+        if (o.score) psl_score(st, m->logits, (int)f.vocab_size, (int64_t)f.vocab_size, bs, m->score_targets, m->score_scratch, m->score_out);
+        else if (o.sampled) psl_sample(st, m->logits, (int)f.vocab_size, m->sample_dev, m->sample_scratch, nullptr, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
         else if (sq) {
             psl_argmax2(st, m->logits, f.vocab_size, bs, m->argmax_dev, m->am_v, m->am_i, nullptr, nullptr, nullptr);
             if (advance) psl_seqs_advance(st, m->seq_tab, m->argmax_dev, m->tokens_dev, m->seq_ids_dev, bs);
@@ -721,6 +726,41 @@ int ps_hip_model_forward_lowered(ps_hip_model *m, const int32_t *tokens, int n, 
 // cache advanced after each -- with the SAME bits, but up to max_batch / chunk reference chunks per launch sequence ("super-chunk"): every
 // mat-mul of a layer sees all their columns at once (per-chunk fixed costs paid a quarter as often at chunk 128 / max_batch 512), only the
 // attention is evaluated per reference chunk (fwd_opts::attn_chunk).  8B, chunk 128: 14.4 k -> ~17 k tok/s.
+// The super-chunk loop of ps_hip_model_prefill and ps_hip_model_score (the caller has checked its arguments): `per` reference chunks per launch sequence.
+// With targets / out_host the lm_head runs for every column and the scoring launches behind it; the records come back per super-chunk, and a row whose
+// certificate did not close is redone from the logits buffer, which still holds it.
+static int append_chunks(ps_hip_model *m, const int32_t *tokens, int n, int chunk, int per, const char *who, const int32_t *targets, ps_score *out_host) {
+    ps_hip_ctx *c = m->ctx;
+    const bool score = targets != nullptr;
+    m->pin_argmax_n = 0;
+    if (per > 64) per = 64;
+    if (per < 1) per = 1;
+    for (int done = 0; done < n;) {
+        const int ns = n - done < per * chunk ? n - done : per * chunk;
+        const int pos = (int)m->cur().position;
+        const int rc = with_attn_retry(m, [&]() -> int { // (per super-chunk: the ones before it have advanced the position)
+            PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens + done, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
+            if (score) PS_CHECK(c, hipMemcpyAsync(m->score_targets, targets + done, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, pos, ns, 0);
+            hipLaunchKernelGGL(set_sub_states_kernel, dim3(1), dim3(64), 0, c->stream, m->state_sub, pos, chunk, ns);
+            fwd_opts o;
+            o.lm_head = score; o.score = score; o.n_kv_host = pos + ns; o.attn_chunk = chunk;
+            if (int rc_fw = enqueue_forward(m, ns, o)) return rc_fw;
+            if (ns == 1) note_single_token(m);
+            if (score) PS_CHECK(c, hipMemcpyAsync(out_host + done, m->score_out, (size_t)ns * sizeof(ps_score), hipMemcpyDeviceToHost, c->stream));
+            PS_CHECK(c, sync_stream(m));
+            return check_attn_timeout(m, who); // a one-token tail: once more, with the two launches
+        });
+        if (rc) return rc;
+        if (score)
+            if (int rc2 = psl_score_finish(c, m->logits, (int)m->cfg.vocab_size, (int64_t)m->cfg.vocab_size, ns, targets + done, out_host + done)) return rc2;
+        unmask_range(m, (size_t)pos, (size_t)ns);
+        m->cur().position += (size_t)ns;
+        done += ns;
+    }
+    return 0;
+}
+
 int ps_hip_model_prefill(ps_hip_model *m, const int32_t *tokens, int n, int chunk) {
     ps_hip_ctx *c = m->ctx;
     if (n <= 0) return 0;
@@ -729,30 +769,30 @@ int ps_hip_model_prefill(ps_hip_model *m, const int32_t *tokens, int n, int chun
     if (m->cur().position + (size_t)n > m->cfg.seq_len) PS_FAIL(c, "model_prefill: KV cache is full (n_ctx)");
     if (int rc = check_tokens(m, tokens, n, "model_prefill")) return rc;
     PS_CHECK(c, hipSetDevice(c->device));
-    m->pin_argmax_n = 0;
-    int per = m->max_batch / chunk; // reference chunks per super-chunk
-    if (per > 64) per = 64;
-    if (per < 1) per = 1;
-    for (int done = 0; done < n;) {
-        const int ns = n - done < per * chunk ? n - done : per * chunk;
-        const int pos = (int)m->cur().position;
-        const int rc = with_attn_retry(m, [&]() -> int { // (per super-chunk: the ones before it have advanced the position)
-            PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, tokens + done, (size_t)ns * 4, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, pos, ns, 0);
-            hipLaunchKernelGGL(set_sub_states_kernel, dim3(1), dim3(64), 0, c->stream, m->state_sub, pos, chunk, ns);
-            fwd_opts o;
-            o.n_kv_host = pos + ns; o.attn_chunk = chunk;
-            if (int rc_fw = enqueue_forward(m, ns, o)) return rc_fw;
-            if (ns == 1) note_single_token(m);
-            PS_CHECK(c, sync_stream(m));
-            return check_attn_timeout(m, "model_prefill"); // a one-token tail: once more, with the two launches
-        });
-        if (rc) return rc;
-        unmask_range(m, (size_t)pos, (size_t)ns);
-        m->cur().position += (size_t)ns;
-        done += ns;
+    return append_chunks(m, tokens, n, chunk, m->max_batch / chunk, "model_prefill", nullptr, nullptr);
+}
+
+// ps_hip_model_prefill with logits: the same super-chunks (the lm_head is column-wise like every other mat-mul), every column scored on the device behind
+// the lm_head.  One exception to "the same": in the fp16-KV mode (mode bit 3) at chunk 1 every token is a launch sequence of its own, since that mode's
+// attention serves single-token forwards only -- there the cache rows are those of single-token forwards in that mode, not prefill's.
+int ps_hip_model_score(ps_hip_model *m, const int32_t *tokens, const int32_t *targets, int n, int chunk, ps_score *out_host) {
+    ps_hip_ctx *c = m->ctx;
+    if (n <= 0) return 0;
+    if (int rc = settle_pending(m)) return rc;
+    if (chunk <= 0 || chunk > m->max_batch) PS_FAIL(c, "model_score: chunk size out of range");
+    if (m->cur().position + (size_t)n > m->cfg.seq_len) PS_FAIL(c, "model_score: KV cache is full (n_ctx)");
+    if (int rc = check_tokens(m, tokens, n, "model_score")) return rc;
+    if (m->mode & 32) PS_FAIL(c, "model_score: not in the fp16 prefill perf mode (mode bit 5: its batches have no logits)");
+    const int vocab = (int)m->cfg.vocab_size;
+    if (int rc = psl_score_check(c, vocab, targets, n, "model_score")) return rc;
+    PS_CHECK(c, hipSetDevice(c->device));
+    if (!m->score_out) { // first use; score_out is assigned last, so a failed allocation is tried again by the next call
+        if (!m->score_scratch && dmalloc(m, &m->score_scratch, psl_score_scratch_bytes(vocab, m->max_batch))) return 1;
+        if (!m->score_targets && dmalloc(m, (void **)&m->score_targets, (size_t)m->max_batch * 4)) return 1;
+        if (dmalloc(m, (void **)&m->score_out, (size_t)m->max_batch * sizeof(ps_score))) return 1;
     }
-    return 0;
+    const bool single = (m->mode & 8) && chunk == 1;
+    return append_chunks(m, tokens, n, chunk, single ? 1 : m->max_batch / chunk, "model_score", targets, out_host);
 }
 
 int ps_hip_model_forward_tree(ps_hip_model *m, const int32_t *tokens, int n, const int32_t *rope_pos, const uint8_t *tree, int lm_head,

@@ -112,3 +112,10 @@ size_t psl_sample_scratch_bytes(int n_vocab);
 // penalty + top-k + tail + draw of one row of n logits; token_out (device) optional; with state != NULL also the decode
 // bookkeeping of psl_argmax2: token[0] = id, ids[state->n_out++] = id, state->pos0++
 void psl_sample(hipStream_t st, const float *logits, int n, ps_sample_dev *d, void *scratch, int32_t *token_out, ps_step_state *state, int32_t *tokens, int32_t *ids);
+
+// scoring (k_score.hip): three launches over rows x n logits (row r at logits + r * stride), targets and records on the device; then, with the records on the
+// host and the stream idle, psl_score_finish redoes the flagged rows exactly and counts
+size_t psl_score_scratch_bytes(int n_vocab, int rows);
+void psl_score(hipStream_t st, const float *logits, int n, int64_t stride, int rows, const int32_t *targets_dev, void *scratch, ps_score *out_dev);
+int psl_score_check(ps_hip_ctx *c, int n_vocab, const int32_t *targets, int rows, const char *who);
+int psl_score_finish(ps_hip_ctx *c, const float *logits_dev, int n, int64_t stride, int rows, const int32_t *targets, ps_score *out);

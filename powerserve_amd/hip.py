@@ -35,6 +35,7 @@ EXPORTS = [
     "ps_hip_soft_max", "ps_hip_model_kv_copy", "ps_hip_model_kv_save_tokens", "ps_hip_model_kv_unmask_tokens", "ps_hip_model_kv_append_tokens", "ps_hip_model_argmax",
     "ps_hip_sample_covered", "ps_hip_sample", "ps_hip_model_decode_sampled", "ps_hip_sample_counters", "ps_hip_last_sample_kernels",
     "ps_hip_model_seq_reserve", "ps_hip_model_seq_count", "ps_hip_model_seq_position", "ps_hip_model_seq_select", "ps_hip_model_decode_batch", "ps_hip_model_decode_batch_greedy",
+    "ps_hip_score_rows", "ps_hip_model_score", "ps_hip_score_counters",
 ]
 SAMPLE_K_MAX, SAMPLE_WINDOW_MAX = 256, 1024  # PS_SAMPLE_K_MAX, PS_SAMPLE_WINDOW_MAX (include/ps_hip.h)
 
@@ -75,6 +76,9 @@ class SampleState(C.Structure):
     def engine(self):
         return np.array(self.mt[:], dtype=np.uint32), int(self.mt_pos)
 
+SCORE_EXACT, SCORE_OUTSIDE, SCORE_NO_TARGET = 1, 2, 4  # ps_score::flags (include/ps_hip.h)
+SCORE_DTYPE = np.dtype([("prob", np.float32), ("max_logit", np.float32), ("argmax", np.int32), ("flags", np.uint32)])  # ps_score
+DEBUG_SCORE_EPS_SHIFT = 12  # ps_hip_debug_set key: the scoring certificate's eps x 2^value
 
 
 class PSTensor(C.Structure):
@@ -171,6 +175,8 @@ def lib() -> C.CDLL:
         "ps_hip_model_seq_select": (i32, [vp, i32]), "ps_hip_model_decode_batch": (i32, [vp, vp, vp, i32, i32, vp]),
         "ps_hip_model_decode_batch_greedy": (i32, [vp, vp, vp, i32, i32, vp]), "ps_hip_sample_counters": (None, [vp, i32]),
         "ps_hip_last_sample_kernels": (C.c_char_p, []),
+        "ps_hip_score_rows": (i32, [vp, vp, i32, i64, i32, vp, vp]), "ps_hip_model_score": (i32, [vp, vp, vp, i32, i32, vp]),
+        "ps_hip_score_counters": (None, [vp, i32]),
         "ps_hip_debug_f16_gemm": (i32, [vp, i32, C.c_int64, C.c_int64, i32, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -404,6 +410,17 @@ class Model:
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         self.ctx.check(self.ctx.L.ps_hip_model_prefill(self.h, _ptr(tokens), tokens.size, int(chunk)))
 
+    def score(self, tokens, targets, chunk: int) -> np.ndarray:
+        """prefill(tokens, chunk) that also runs the lm_head and scores column i against targets[i] (-1: none): SCORE_DTYPE records, prob bit for bit what
+        the reference's perplexity tool computes (ps_hip_model_score)."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        targets = np.ascontiguousarray(targets, dtype=np.int32)
+        if tokens.size != targets.size:
+            raise ValueError("score: one target per token")
+        out = np.zeros(tokens.size, dtype=SCORE_DTYPE)
+        self.ctx.check(self.ctx.L.ps_hip_model_score(self.h, _ptr(tokens), _ptr(targets), tokens.size, int(chunk), _ptr(out)))
+        return out
+
     def forward_tree(self, tokens, rope_pos, tree=None, lm_head=True, want_logits=False, advance=False):
         """Token-tree forward (src/speculative/token_tree.cpp): tokens appended at the current KV position, column i rotated
         with rope_pos[i], visible batch columns given by tree[i][j] (None: causal).  Returns (logits | None, argmax)."""
@@ -561,3 +578,18 @@ def sample_counters(reset: bool = False):
 
 def last_sample_kernels() -> str:
     return lib().ps_hip_last_sample_kernels().decode()
+
+
+def score_rows(ctx: Ctx, logits_dev: int, n_vocab: int, row_stride: int, targets) -> np.ndarray:
+    """Rows of device logits (row r at logits_dev + 4 * r * row_stride bytes) scored against targets (-1: none): SCORE_DTYPE records."""
+    targets = np.ascontiguousarray(targets, dtype=np.int32)
+    out = np.zeros(targets.size, dtype=SCORE_DTYPE)
+    ctx.check(ctx.L.ps_hip_score_rows(ctx.h, C.c_void_p(logits_dev), int(n_vocab), int(row_stride), targets.size, _ptr(targets), _ptr(out)))
+    return out
+
+
+def score_counters(reset: bool = False):
+    """(rows scored, of them on the exact path, rows refused for a NaN / +inf) since the last reset, process-wide"""
+    out = (C.c_uint64 * 3)()
+    lib().ps_hip_score_counters(out, int(reset))
+    return int(out[0]), int(out[1]), int(out[2])

@@ -16,7 +16,8 @@ EXPORTS = ["psh_last_error", "psh_model_load", "psh_model_free", "psh_model_set_
            "psh_model_seq_reserve", "psh_model_seq_select", "psh_model_seq_position", "psh_model_decode_batch",
            "psh_model_set_device_sampling", "psh_sampler_engine_state", "psh_sampler_device_state", "psh_sampler_is_standard", "psh_sampler_append_noop", "psh_model_generate_with_chain",
            "psh_debug_mt_seed", "psh_debug_mt_next", "psh_debug_discrete", "psh_debug_partial_sort", "psh_debug_chain", "psh_debug_std_mt",
-           "psh_debug_std_mt_seed", "psh_debug_std_discrete", "psh_debug_std_partial_sort"]
+           "psh_debug_std_mt_seed", "psh_debug_std_discrete", "psh_debug_std_partial_sort",
+           "psh_model_score", "psh_ppl_create", "psh_ppl_destroy", "psh_ppl_add", "psh_ppl_current", "psh_ppl_logit_sum", "psh_ppl_n_tokens", "psh_debug_score_row", "psh_debug_score_certify"]
 _LIB = None
 
 
@@ -84,6 +85,22 @@ def lib() -> C.CDLL:
         L.psh_debug_std_discrete.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.psh_debug_std_partial_sort.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.psh_gguf_summary.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
+        L.psh_model_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.psh_ppl_create.restype = C.c_void_p
+        L.psh_ppl_create.argtypes = [C.c_int]
+        L.psh_ppl_destroy.argtypes = [C.c_void_p]
+        L.psh_ppl_add.restype = C.c_float
+        L.psh_ppl_add.argtypes = [C.c_void_p, C.c_int32, C.c_float]
+        L.psh_ppl_current.restype = C.c_float
+        L.psh_ppl_current.argtypes = [C.c_void_p]
+        L.psh_ppl_logit_sum.restype = C.c_float
+        L.psh_ppl_logit_sum.argtypes = [C.c_void_p]
+        L.psh_ppl_n_tokens.restype = C.c_int64
+        L.psh_ppl_n_tokens.argtypes = [C.c_void_p]
+        L.psh_debug_score_row.restype = C.c_float
+        L.psh_debug_score_row.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.psh_debug_score_certify.restype = C.c_uint32
+        L.psh_debug_score_certify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -169,6 +186,18 @@ class HostModel:
         t = np.ascontiguousarray(tokens, dtype=np.int32)
         if self.L.psh_model_prefill(self.h, t.ctypes.data, t.size, int(batch_size)):
             raise HostError(self.L.psh_last_error().decode())
+
+    def score(self, tokens, targets, batch_size: int) -> np.ndarray:
+        """Model::score: prefill in chunks of batch_size with the lm_head, column i scored against targets[i] (-1: none); hip.SCORE_DTYPE records."""
+        from . import hip
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        g = np.ascontiguousarray(targets, dtype=np.int32)
+        if t.size != g.size:
+            raise ValueError("score: one target per token")
+        out = np.zeros(t.size, dtype=hip.SCORE_DTYPE)
+        if self.L.psh_model_score(self.h, t.ctypes.data, g.ctypes.data, t.size, int(batch_size), out.ctypes.data):
+            raise HostError(self.L.psh_last_error().decode())
+        return out
 
     # ---- sequences (Model::reserve_sequences / select_sequence / decode_batch)
     def reserve_sequences(self, n_seq: int):
@@ -491,3 +520,48 @@ class Workspace:
         self.main.close()
         if self.draft is not None:
             self.draft.close()
+
+
+class PerplexityCalculator:
+    """The reference's PerplexityCalculator (app/perplexity/main.cpp:29-61) through the C++ facade: a float sum of std::log(prob), exp(-sum / n_tokens)."""
+
+    def __init__(self, n_vocabs: int):
+        self.L = lib()
+        self.h = self.L.psh_ppl_create(int(n_vocabs))
+
+    def add(self, token: int, prob) -> float:
+        """apply + accept of one scored position; returns current_ppl"""
+        return float(self.L.psh_ppl_add(self.h, int(token), C.c_float(float(prob))))
+
+    @property
+    def current_ppl(self) -> float:
+        return float(self.L.psh_ppl_current(self.h))
+
+    @property
+    def logit_sum(self) -> float:
+        return float(self.L.psh_ppl_logit_sum(self.h))
+
+    @property
+    def n_tokens(self) -> int:
+        return int(self.L.psh_ppl_n_tokens(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.psh_ppl_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def score_row_exact(x: np.ndarray, t: int) -> np.float32:
+    """ProbArray::softmax's own operations on one row (the library's exact path): the target's probability"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    return np.float32(lib().psh_debug_score_row(x.ctypes.data, x.size, int(t)))
+
+
+def score_row_certify(x: np.ndarray, t: int, shift: int = 0):
+    """The device's fast path on the CPU (its order of additions, the certificate with eps x 2^shift): (flags, prob, max_logit, argmax)"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    p, m, a = C.c_float(), C.c_float(), C.c_int32()
+    fl = lib().psh_debug_score_certify(x.ctypes.data, x.size, int(t), int(shift), C.byref(p), C.byref(m), C.byref(a))
+    return int(fl), np.float32(p.value), np.float32(m.value), int(a.value)

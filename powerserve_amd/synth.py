@@ -30,6 +30,9 @@ PRESETS = {
     # small shapes for parity tests (finish in seconds on the CPU oracle)
     "tiny-llama": ("llama", 256, 512, 2, 4, 2, 64, 512, 1e4, 0, False, 1e-5),
     "tiny-qwen2": ("qwen2", 256, 512, 2, 4, 2, 64, 512, 1e6, 2, True, 1e-6),
+    # the tiny shapes with a vocabulary that is no multiple of a wave, a slice or a vector of the scoring kernels (tests/test_gpu_score.py)
+    "tiny-llama-v1000": ("llama", 256, 512, 2, 4, 2, 64, 1000, 1e4, 0, False, 1e-5),
+    "tiny-qwen2-v1000": ("qwen2", 256, 512, 2, 4, 2, 64, 1000, 1e6, 2, True, 1e-6),
     "small-llama": ("llama", 512, 1536, 3, 8, 2, 64, 2048, 5e5, 0, True, 1e-5),
     "small-llama-hs128": ("llama", 1024, 2048, 2, 8, 2, 128, 1024, 5e5, 0, False, 1e-5),
     # a draft model for small-llama-hs128: same vocabulary, different width / depth / head size
