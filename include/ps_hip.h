@@ -134,6 +134,7 @@ int ps_hip_rms_norm(ps_hip_ctx *ctx, const ps_tensor *dst, const ps_tensor *src,
 /* pos: HOST int32[n_pos] (the reference passes a std::vector<int>, executor.cpp:123-128) */
 int ps_hip_rope(ps_hip_ctx *ctx, const ps_tensor *dst, const ps_tensor *src, const int32_t *pos, int n_pos,
                 const ps_rope_params *rp);
+/* rows of up to 150 KiB stay in LDS; longer ones, up to PS_HIP_LONG_CTX_MAX + 64 elements (contiguous F32), take the long-window row routine (same bits) */
 int ps_hip_softmax_ext(ps_hip_ctx *ctx, const ps_tensor *dst, const ps_tensor *src, const ps_tensor *mask,
                        float scale, float max_bias);
 /* GGMLBackend::softmax (backend/ggml/ggml_wrapper.cpp:57-69) -> powerserve_compute_forward_soft_max (ggml.c:15060-15089): the same
@@ -171,6 +172,22 @@ typedef struct {
 } ps_model_desc;
 
 int ps_hip_model_create(ps_hip_ctx *ctx, const ps_model_desc *desc, ps_hip_model **out);
+/* Long windows.  ps_hip_model_create keeps a forward's soft-max rows in LDS and refuses a window they do not fit in ("n_ctx too large": 7 296 slots at 4 query
+ * heads per kv head, 3 648 at 8).  ps_hip_model_create_long is ps_hip_model_create for a LONG-WINDOW model: any n_ctx that is a multiple of 4, up to
+ * PS_HIP_LONG_CTX_MAX.  Its attention keeps score and probability rows in device memory: EVERY forward (single tokens, batches, prefill super-chunks, tree
+ * forwards, hidden slots, ps_hip_model_score, the decode loops, the lowered forward) runs the score kernel, attn_softmax_long_kernel and a V.p kernel
+ * (attn_pv_long_kernel below 8 columns, the matrix-core kernels from 8 on) -- bit for bit what a regular model computes, at any depth.  The fused head, the
+ * one-launch attention and the fp16-KV kernel are never chosen: mode bits 4 and 7 are accepted and change nothing; mode bit 3 and ps_hip_model_seq_reserve
+ * beyond one sequence are refused (rc 2, nothing changed; the batched step's kernels hold LDS rows).  The property is fixed at creation.
+ * The score buffer is max_batch * n_heads * n_ctx * 4 bytes and the FP32 KV cache 2 * n_layers * n_ctx * kv_dim * 4: rc 1 when the device has no room. */
+#define PS_HIP_LONG_CTX_MAX 131072
+int ps_hip_model_create_long(ps_hip_ctx *ctx, const ps_model_desc *desc, ps_hip_model **out);
+int ps_hip_model_is_long(const ps_hip_model *m);
+/* diagnostics: [0] rows soft-maxed by the long kernels (attention rows and ps_hip_softmax_ext rows above the LDS-resident kernel's cap), [1] of them through the
+ * sequential sum -- the row sum is formed in the device's order and CERTIFIED to give the reference's (float)(1 / sum), else redone in the reference's order
+ * (csrc/ps_softmax_long_dev.h).  Process-wide (per loaded library: the default and the -DPS_CONTRACT build count their own launches), since the last reset;
+ * waits for the devices that ran such a kernel. */
+void ps_hip_softmax_long_counters(uint64_t *out2, int reset);
 void ps_hip_model_destroy(ps_hip_model *m);
 /* KVCacheInterface bookkeeping (core/kv_cache.hpp:97-163) */
 size_t ps_hip_model_kv_position(const ps_hip_model *m);
@@ -334,6 +351,7 @@ int ps_hip_model_bench_matmul(ps_hip_model *m, int reps, int which, int bs, doub
 /* diagnostics: the kernel (rocprofv3's template name) the most recent quantized mat-mul launch of this process went to */
 const char *ps_hip_last_matmul_kernel(void);
 /* diagnostics: the single-token attention the most recent single-token forward of this process enqueued (rocprofv3's template name):
+ * (a long-window model: "attn_scores_kernel<NV> + attn_softmax_long_kernel + attn_pv_long_kernel<KVS>" below 8 columns, "attn_scores_mfma_kernel<NV> + attn_softmax_long_kernel + attn_pv_mfma" from 8 on, noted by every forward)
  * "qkv_attn_kernel<NV, KVS>" (fused with the Q / K / V mat-vec), "attn_decode2_kernel<NV, NT, KVS>" (one launch), "attn_scores_kernel<NV> + attn_softmax_pv_kernel"
  * (two launches, mode bit 4) or "attn_flash16_kernel<HS>" (fp16-KV decode mode, bit 3); "" before any.  Noted at enqueue time: after a captured step's
  * replay it names what the capture enqueued. */
@@ -350,6 +368,8 @@ int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_wo
  * with plain (0) or non-temporal (1) loads whatever the cache's size, -1 (default): by the rule of csrc/model.hip (a cache-policy hint: no result bit depends on it); key 10: F16 batches on the matrix cores (0, default) or on the VALU chain kernel (1: A/B only, same bits);
  * key 11: the fused launch's first rendezvous on tagged granules (0, default) or on the counter (1: A/B and fallback);
  * key 12: the scoring certificate's eps (csrc/ps_score_dev.h) multiplied by 2^value, 0 <= value <= 100 (default 0; tests and A/B only: eps >= 1 sends every row down the exact path).
+ * key 13: long-window models, positions per LDS tile of attn_pv_long_kernel: a multiple of 32 up to 2048, 0 = the default (2048); read at enqueue time (tests: several tiles at a small window);
+ * key 14: the long soft-max's row-sum certificate, eps (csrc/ps_softmax_long_dev.h) multiplied by 2^value, 0 <= value <= 100 (default 0; tests: at 100 every row takes the sequential sum).
  * Returns non-zero for an unknown key.  (A captured single-token step keeps the launch plan it was captured with: ps_hip_model_set_mode drops it.) */
 int ps_hip_debug_set(int key, int value);
 /* Diagnostic: one GEMM shape of the fp16 perf mode on synthetic operands (tools/f16_gemm_bench.py): out[M][N] = x[M][K] . W[N][K]^T, timed over

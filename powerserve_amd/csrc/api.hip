@@ -380,8 +380,14 @@ int ps_hip_soft_max(ps_hip_ctx *c, const ps_tensor *dst, const ps_tensor *src) {
 
 int ps_hip_softmax_ext(ps_hip_ctx *c, const ps_tensor *dst, const ps_tensor *src, const ps_tensor *mask, float scale, float max_bias) {
     if (max_bias != 0.0f) PS_FAIL(c, "softmax_ext: ALiBi (max_bias != 0) is not on PowerServe's path");
-    if (src->ne[0] * 4 > 150 * 1024) PS_FAIL(c, "softmax_ext: row too long for the LDS-resident kernel");
-    psl_softmax_ext(c->stream, dst, src, mask ? (const float *)mask->data : nullptr, scale);
+    const float *mp = mask ? (const float *)mask->data : nullptr;
+    if (src->ne[0] * 4 > 150 * 1024) { // rows above the LDS-resident kernel's cap: the long-window row routine (k_attn_long.hip), rows in device memory
+        if (src->ne[0] > PS_HIP_LONG_CTX_MAX + 64) PS_FAIL(c, "softmax_ext: row too long (more than PS_HIP_LONG_CTX_MAX + 64 elements)");
+        if (src->dtype != PS_F32 || dst->dtype != PS_F32 || src->nb[0] != 4 || dst->nb[0] != 4) PS_FAIL(c, "softmax_ext: long rows must be contiguous F32");
+        psl_softmax_long_ext(c->stream, dst, src, mp, scale);
+    } else {
+        psl_softmax_ext(c->stream, dst, src, mp, scale);
+    }
     PS_CHECK(c, hipGetLastError());
     return 0;
 }
@@ -498,7 +504,7 @@ int ps_hip_debug_timeline(ps_hip_ctx *ctx, int key, uint64_t *host_out, int n_wo
 }
 
 int ps_hip_debug_set(int key, int value) {
-    extern int g_g4k_par, g_f16_variant, g_force_attn_timeout, g_qa_force, g_kv_stream_force, g_f16_batch, g_qa_counter, g_score_shift;
+    extern int g_g4k_par, g_f16_variant, g_force_attn_timeout, g_qa_force, g_kv_stream_force, g_f16_batch, g_qa_counter, g_score_shift, g_sml_shift;
     // (keys 1 and 2, the mat-vec's wave configuration and a what-if word, left with the configurations they selected, key 6 with the A/B of the wide mat-mul's item order: unknown keys now; there never was a key 8)
     if (key == 3) { g_g4k_par = value; return 0; } // the narrow-batch Q4_K mat-mul for few row tiles: 0 gemm4k_par_kernel off (A/B), 4 / 8 waves per tile, 1 by tile count (default)
     if (key == 4) { g_f16_variant = value; return 0; } // the fp16 perf mode's GEMM: 0 by shape, 1 / 2 one tile form
@@ -507,6 +513,8 @@ int ps_hip_debug_set(int key, int value) {
     if (key == 9) { g_kv_stream_force = value; return 0; } // single-token attention: the cached K / V with plain (0) / non-temporal (1) loads whatever the cache's size; -1: by size (model.hip)
     if (key == 10) { g_f16_batch = value; return 0; } // F16 batches: 0 matrix cores (default), 1 VALU chains (A/B)
     if (key == 11) { g_qa_counter = value; return 0; } // the fused launch's rendezvous A: 0 granules (default), 1 the counter (A/B, fallback); read at enqueue: captured graphs keep theirs
+    if (key == 13) return psl_attn_long_set_tile(value); // long-window V.p (k_attn_long.hip): positions per LDS tile, a multiple of 32 up to 2048; 0 = default.  Read at enqueue: captured graphs keep theirs
+    if (key == 14) { if (value < 0 || value > 100) return 1; g_sml_shift = value; return 0; } // long-window soft-max: the row-sum certificate's eps x 2^value (100: every row takes the sequential sum; tests)
     if (key == 12) { if (value < 0 || value > 100) return 1; g_score_shift = value; return 0; } // scoring: the certificate's eps x 2^value (tests, A/B; k_score.hip)
     return 1;
 }

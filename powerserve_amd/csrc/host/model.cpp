@@ -92,7 +92,7 @@ static Tensor upload(hip::HIPBackend &be, const GGUFFile &f, const std::string &
 }
 
 Model::Model(const std::string &model_dir, const std::shared_ptr<ModelConfig> &config, const std::shared_ptr<Platform> &platform, int device,
-             size_t max_batch) :
+             size_t max_batch, bool long_window) :
     m_filename(model_dir + "/ggml/weights.gguf"), m_config(config), m_platform(platform) {
     m_is_need_bias = config->arch == "qwen2";
     HyperParams hp;
@@ -140,7 +140,8 @@ Model::Model(const std::string &model_dir, const std::shared_ptr<ModelConfig> &c
     d.ffn_gate = wg.data(); d.ffn_up = wu.data(); d.ffn_down = wd.data();
     if (m_is_need_bias) { d.attn_q_bias = bq.data(); d.attn_k_bias = bk.data(); d.attn_v_bias = bv.data(); }
     ps_hip_model *pm = nullptr;
-    if (ps_hip_model_create(be.m_ctx, &d, &pm)) POWERSERVE_ABORT(std::string("ps_hip_model_create: ") + ps_hip_last_error(be.m_ctx));
+    if (long_window ? ps_hip_model_create_long(be.m_ctx, &d, &pm) : ps_hip_model_create(be.m_ctx, &d, &pm))
+        POWERSERVE_ABORT(std::string("ps_hip_model_create: ") + ps_hip_last_error(be.m_ctx));
     hip::LoweringTable lt;
     lt.token_embd = d.token_embd; lt.output = d.output; lt.output_norm = d.output_norm; lt.bias = m_is_need_bias;
     for (uint32_t i = 0; i < L; i++) lt.layers.push_back({an[i], wq[i], wk[i], wv[i], bq[i], bk[i], bv[i], wo[i], fn[i], wg[i], wu[i], wd[i]});
@@ -382,12 +383,12 @@ auto Model::generate(const std::vector<Token> &prompt, int steps, size_t batch_s
     return out;
 }
 
-auto load_model(const std::string &model_dir, const std::shared_ptr<Platform> &platform, int device, size_t max_batch, int n_ctx_cap)
+auto load_model(const std::string &model_dir, const std::shared_ptr<Platform> &platform, int device, size_t max_batch, int n_ctx_cap, bool long_window)
     -> std::shared_ptr<Model> {
     auto config = std::make_shared<ModelConfig>(model_dir + "/model.json");
     if (n_ctx_cap > 0) config->llm.seq_len = (uint32_t)n_ctx_cap; // explicit cap: the FP32 KV cache is sized by n_ctx
     if (config->arch != "llama" && config->arch != "qwen2") POWERSERVE_ABORT("unknown model type: " + config->arch);
-    return std::make_shared<Model>(model_dir, config, platform, device, max_batch);
+    return std::make_shared<Model>(model_dir, config, platform, device, max_batch, long_window);
 }
 
 } // namespace powerserve
@@ -403,6 +404,14 @@ void *psh_model_load(const char *model_dir, int device, int max_batch, int n_ctx
         auto h = new psh_model();
         h->platform = std::make_shared<Platform>();
         h->model = load_model(model_dir, h->platform, device, (size_t)max_batch, n_ctx_cap);
+        return h;
+    } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+void *psh_model_load_long(const char *model_dir, int device, int max_batch, int n_ctx_cap, int long_window) { // psh_model_load with load_model's long_window argument
+    try {
+        auto h = new psh_model();
+        h->platform = std::make_shared<Platform>();
+        h->model = load_model(model_dir, h->platform, device, (size_t)max_batch, n_ctx_cap, long_window != 0);
         return h;
     } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
 }

@@ -63,7 +63,7 @@ struct Model {
     bool m_device_sampling = true; // generate(.., SamplerChain &): a standard chain the device covers runs inside the captured step; false: the host loop
 
     Model(const std::string &model_dir, const std::shared_ptr<ModelConfig> &config, const std::shared_ptr<Platform> &platform, int device,
-          size_t max_batch);
+          size_t max_batch, bool long_window = false);
     virtual ~Model();
 
     // one forward over `tokens` at consecutive positions `pos`; lm_head: logits for every token
@@ -109,8 +109,9 @@ private:
 using LlamaModel = Model;
 using Qwen2Model = Model;
 
-auto load_model(const std::string &model_dir, const std::shared_ptr<Platform> &platform, int device = 0, size_t max_batch = 128, int n_ctx_cap = 0)
-    -> std::shared_ptr<Model>;
+// long_window: a long-window device model (ps_hip_model_create_long): any n_ctx up to PS_HIP_LONG_CTX_MAX, attention rows in device memory, one sequence
+auto load_model(const std::string &model_dir, const std::shared_ptr<Platform> &platform, int device = 0, size_t max_batch = 128, int n_ctx_cap = 0,
+                bool long_window = false) -> std::shared_ptr<Model>;
 
 // the device sampler's view of a standard chain (configuration, engine, fixed penalty window); false: not expressible
 bool device_sampler_state(const SamplerChain &sampler, ps_sample_cfg &c, ps_sample_state &st);

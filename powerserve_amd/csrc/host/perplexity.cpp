@@ -1,10 +1,12 @@
-// Model::score (the façade over ps_hip_model_score), the PerplexityCalculator's C driver, and the CPU build of the scoring arithmetic
-// (csrc/ps_score_dev.h, the same source the kernels of csrc/k_score.hip compile) exported as psh_debug_score_* for tests/test_score_cpu.py.
+// Model::score (the façade over ps_hip_model_score), the PerplexityCalculator's C driver, and the CPU builds of the scoring arithmetic
+// (csrc/ps_score_dev.h, the same source the kernels of csrc/k_score.hip compile) exported as psh_debug_score_* for tests/test_score_cpu.py and of the long
+// soft-max's row sum (csrc/ps_softmax_long_dev.h) exported as psh_debug_softmax_long_sum for tests/test_long_ctx_cpu.py.
 #include "perplexity.hpp"
 
 #include "model.hpp"
 
 #include "../ps_score_dev.h"
+#include "../ps_softmax_long_dev.h"
 
 using namespace powerserve;
 
@@ -52,5 +54,9 @@ float psh_debug_score_row(const float *x, int n, int t) { return ps_score_row_ex
 uint32_t psh_debug_score_certify(const float *x, int n, int t, int shift, float *prob, float *max_out, int32_t *argmax_out) {
     return ps_score_row_fast(x, n, t, shift, prob, max_out, argmax_out);
 }
+
+// ---- ps_softmax_long_dev.h, CPU build: one row of n soft-max numerators through the long kernels' row sum.  *inv_fast = (float)(1 / S), S summed by `lanes`
+// lanes in an order of their own; *inv_seq = the reference's factor (its sequential sum).  Returns 1 when the certificate (eps x 2^shift) closed on S
+int psh_debug_softmax_long_sum(const float *e, int n, int lanes, int shift, float *inv_fast, float *inv_seq) { return ps_sml_row(e, n, lanes, shift, inv_fast, inv_seq); }
 
 } // extern "C"

@@ -1533,6 +1533,21 @@ bool psl_attn_pv_quantizes(const psl_attn_args &a, int bs) {
     const int r2 = a.n_heads / a.n_kv_heads;
     return bs >= 8 && a.head_size == 128 && (r2 == 2 || r2 == 4 || r2 == 8) && a.qact.qs != nullptr;
 }
+void psl_attn_pv_mfma(hipStream_t st, const psl_attn_args &a, int bs) {
+    const int r2p = a.n_heads / a.n_kv_heads;
+    const dim3 gpv((unsigned)((bs * r2p + 15) / 16), (unsigned)a.n_kv_heads);
+    if (a.head_size == 128 || a.head_size == 64) {
+        static unsigned long long attrl = 0;
+        if (ps_first_on_device(&attrl)) {
+            (void)hipFuncSetAttribute((const void *)attn_pv_mfma_lds_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+            (void)hipFuncSetAttribute((const void *)attn_pv_mfma_lds_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+        }
+        if (a.head_size == 128) hipLaunchKernelGGL(attn_pv_mfma_lds_kernel<8>, gpv, dim3(512), 2 * 9 * 16 * PVM_RS * 4, st, a);
+        else hipLaunchKernelGGL(attn_pv_mfma_lds_kernel<4>, gpv, dim3(256), 2 * 5 * 16 * PVM_RS * 4, st, a);
+        return;
+    }
+    hipLaunchKernelGGL(attn_pv_mfma_kernel, gpv, dim3((unsigned)(a.head_size / 16 * 64)), 0, st, a);
+}
 void psl_attn_softmax_pv(hipStream_t st, const psl_attn_args &a, int bs) {
     if (bs >= 8 && a.head_size % 16 == 0) { // prefill chunks / wide trees: soft-max in place, then V·p on the matrix cores
         static unsigned long long attrp = 0; // devices that have the attribute
@@ -1541,18 +1556,7 @@ void psl_attn_softmax_pv(hipStream_t st, const psl_attn_args &a, int bs) {
         const size_t ldsp = (size_t)r2p * (((size_t)a.n_ctx + 3) & ~(size_t)3) * 4;
         if (a.n_ctx <= 64 * 4 * SMW_MAXQ) hipLaunchKernelGGL(attn_softmax_probs_wave_kernel, dim3((unsigned)((bs * a.n_heads + 3) / 4)), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(attn_softmax_probs_kernel, dim3((unsigned)a.n_kv_heads, (unsigned)bs), dim3(PV_NT), ldsp, st, a);
-        const dim3 gpv((unsigned)((bs * r2p + 15) / 16), (unsigned)a.n_kv_heads);
-        if (a.head_size == 128 || a.head_size == 64) {
-            static unsigned long long attrl = 0;
-            if (ps_first_on_device(&attrl)) {
-                (void)hipFuncSetAttribute((const void *)attn_pv_mfma_lds_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-                (void)hipFuncSetAttribute((const void *)attn_pv_mfma_lds_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-            }
-            if (a.head_size == 128) hipLaunchKernelGGL(attn_pv_mfma_lds_kernel<8>, gpv, dim3(512), 2 * 9 * 16 * PVM_RS * 4, st, a);
-            else hipLaunchKernelGGL(attn_pv_mfma_lds_kernel<4>, gpv, dim3(256), 2 * 5 * 16 * PVM_RS * 4, st, a);
-            return;
-        }
-        hipLaunchKernelGGL(attn_pv_mfma_kernel, gpv, dim3((unsigned)(a.head_size / 16 * 64)), 0, st, a);
+        psl_attn_pv_mfma(st, a, bs);
         return;
     }
     if (bs > 1) { // batches: one workgroup per (kv head, column pair)

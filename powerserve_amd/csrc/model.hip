@@ -49,6 +49,7 @@ struct ps_hip_model {
     ps_llm_config cfg{};
     bool qwen2 = false;
     int max_batch = 1;
+    bool long_window = false; // ps_hip_model_create_long: score / probability rows in device memory (k_attn_long.hip), fixed at creation
     const ps_weight *token_embd = nullptr, *output = nullptr;
     const float *output_norm = nullptr;
     std::vector<const float *> attn_norm, ffn_norm, bq, bk, bv;
@@ -124,6 +125,9 @@ static void drop_graphs(ps_hip_model *m) { // every captured launch plan (they b
 static void graph_drop_if_stale(step_graph &g, size_t pos) {
     if (pos < g.hint || pos >= g.hint + 1024) graph_drop(g);
 }
+// long-window models: the score grid of a step captured at `hint` covers the slots it can meet before graph_drop_if_stale drops it (n_kv <= hint + 1024), not
+// n_ctx -- 32 768 mostly empty workgroups per layer at 131 072 slots
+static size_t graph_window_end(const ps_hip_model *m, size_t hint) { return std::min<size_t>(hint + 1024, m->cfg.seq_len); }
 // capture what `enqueue` puts on the stream into g (nothing executes), with `pos` as its hint.  False: g is empty, and c->err says why
 template <class F> static bool graph_capture(ps_hip_model *m, step_graph &g, size_t pos, F &&enqueue) {
     ps_hip_ctx *c = m->ctx;
@@ -251,6 +255,7 @@ struct fwd_opts {
     // attention go per column to that sequence's cache (k_attn.hip, "batched decode")
     const psl_seqs_args *sq = nullptr;
     int n_kv_host = 0;     // pos0 + bs of a forward that is enqueued eagerly (0 while a graph is captured / replayed)
+    int n_kv_grid = 0;     // long-window models, with n_kv_host == 0 (a captured or device-positioned single-token step): an upper bound of n_kv that sizes the score grid
     int n_kv_hint = 0;     // capture of a single-token forward: the lower bound of n_kv its prefetch hint is baked with
     int attn_chunk = 0;    // > 0: a super-chunk (ps_hip_model_prefill), the attention runs chunk by chunk
 };
@@ -275,14 +280,16 @@ static int enqueue_forward(ps_hip_model *m, int bs, const fwd_opts &o) {
     aa.rope_pos = use_rope_pos ? m->rope_pos_dev : nullptr;
     aa.kv_vis = kv.n_hidden ? kv.kv_vis_dev : nullptr;
     aa.scale = 1.0f / sqrtf((float)f.head_size);
-    aa.n_kv_host = o.n_kv_host;
+    aa.n_kv_host = o.n_kv_host > 0 ? o.n_kv_host : o.n_kv_grid; // (without bs_host it only sizes the score grid)
     aa.bs_host = o.n_kv_host > 0 ? bs : 0;
     aa.sync = m->attn_sync;
     // fp16 perf mode (NOT bit-exact, mode bit 5): the layer mat-muls of a prefill batch as dense fp16 GEMMs (perf16.hip); single tokens,
     // tree forwards and anything that produces logits stay on the parity kernels
     const bool f16 = (m->mode & 32) && bs >= 2 && !lm_head && !use_tree && !use_rope_pos && !sq;
     if (f16) if (int rc = ensure_perf16(m)) return rc;
-    const bool one_launch = (m->mode & 16) == 0; // default; mode bit 4 switches attn_decode2 off (two launches)
+    const bool lw = m->long_window; // scores, then the long soft-max and V.p, whatever the forward (k_attn_long.hip); the one-launch forms hold LDS rows
+    const bool one_launch = (m->mode & 16) == 0 && !lw; // default; mode bit 4 switches attn_decode2 off (two launches)
+    auto softmax_pv = [&](const psl_attn_args &as, int nb) { if (lw) psl_attn_long_softmax_pv(st, as, nb); else psl_attn_softmax_pv(st, as, nb); };
     aa.xchg = m->attn_xchg; aa.tick = m->attn_tick; aa.gran = m->attn_gran;
     // Single-token attention: are the cached K rows / V channels read with non-temporal loads (psl_attn_args::kv_stream)?  Measured (profiles/r06_kv_stream_threshold.txt,
     // r06_ad2_nt_small_models.txt): the fused Q / K / V + attention launch is faster with them at every cache length tried (8B: +1.0 % behind a 256-token prompt, +1.6 % behind
@@ -319,7 +326,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, const fwd_opts &o) {
                 if (psf16_gemm_n(c, m->pf, 3, W3, n3, dim, m->xh, bs, o3, n3, 0.f)) return 2; // Q, K, V: one launch
             }
             if (m->qwen2) { psf16_add_bias(st, m->q, m->bq[L], dim, bs); psf16_add_bias(st, m->k, m->bk[L], kvd, bs); psf16_add_bias(st, m->v, m->bv[L], kvd, bs); }
-        } else if (bs == 1 && !use_tree && one_launch && !kv16 && g.rope && (m->mode & 128) == 0 &&
+        } else if (bs == 1 && !use_tree && one_launch && !kv16 && g.rope && (m->mode & 128) == 0 && // (one_launch: never in a long-window model)
                    (aa.dbg = psk_gemv_dbg_buf(10, 3), aa.kv_stream = kvs_fused, psk_qkv_attn(st, c->n_cu, g, dim, aa))) { // timeline key 43
             // the head of the layer in ONE launch: Q / K / V mat-vec + RoPE + KV append + single-token attention (k_qkvattn.hip); mode bit 7 brings the two launches back
             aa.dbg = nullptr; aa.kv_stream = kvs_own;
@@ -350,7 +357,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, const fwd_opts &o) {
                 as.bs_host = as.n_kv_host > 0 ? nb : 0;
                 as.qact = ps_act{}; as.dbg = nullptr;
                 psl_attn_scores(st, as, nb);
-                psl_attn_softmax_pv(st, as, nb);
+                softmax_pv(as, nb);
             }
         } else {
             aa.dbg = bs == 1 ? psk_gemv_dbg_buf(10, 0) : nullptr; // timeline key 40
@@ -365,7 +372,7 @@ static int enqueue_forward(ps_hip_model *m, int bs, const fwd_opts &o) {
                 if (!psl_attn_pv_quantizes(aa, bs)) aa.qact = ps_act{};
             }
             att_quantized = aa.qact.qs != nullptr;
-            psl_attn_softmax_pv(st, aa, bs);
+            softmax_pv(aa, bs);
             aa.qact = ps_act{};
             aa.dbg = nullptr;
         }
@@ -484,7 +491,7 @@ static int settle_pending(ps_hip_model *m) {
 
 extern "C" {
 
-int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **out) {
+static int model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **out, const bool long_window) {
     *out = nullptr;
     const ps_llm_config &f = d->cfg;
     if (f.n_kv_heads == 0 || f.n_heads == 0 || f.n_layers == 0 || f.seq_len == 0) PS_FAIL(c, "model_create: zero-sized configuration");
@@ -512,10 +519,13 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
     if (f.n_heads / f.n_kv_heads > 8) PS_FAIL(c, "model_create: GQA ratio > 8 not supported");
     if ((int)f.rope.n_dims != (int)f.head_size) PS_FAIL(c, "model_create: rope n_dims != head_size (reference asserts the same, norm_attention.cpp:38)");
     if (f.seq_len % 4) PS_FAIL(c, "model_create: n_ctx must be a multiple of 4");
-    if ((size_t)(f.n_heads / f.n_kv_heads) * f.seq_len * 4 + 44 * 1024 > 158 * 1024) PS_FAIL(c, "model_create: n_ctx too large for the LDS-resident softmax rows (cap n_ctx)");
+    if (!long_window && (size_t)(f.n_heads / f.n_kv_heads) * f.seq_len * 4 + 44 * 1024 > 158 * 1024)
+        PS_FAIL(c, "model_create: n_ctx too large for the LDS-resident softmax rows (cap n_ctx, or create a long-window model: ps_hip_model_create_long)");
+    if (long_window && f.seq_len > PS_HIP_LONG_CTX_MAX) PS_FAIL(c, "model_create_long: n_ctx above PS_HIP_LONG_CTX_MAX");
     PS_CHECK(c, hipSetDevice(c->device));
     auto m = new ps_hip_model();
     m->ctx = c; m->cfg = f; m->qwen2 = d->is_qwen2 != 0; m->max_batch = d->max_batch > 0 ? d->max_batch : 1;
+    m->long_window = long_window;
     m->mode = mode_env_or() & ~8; // (the fp16-KV mode allocates: only through set_mode)
     m->seqs.resize(1);
     ps_hip_model::seq_state &s0 = m->seqs[0];
@@ -539,7 +549,7 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
         dmalloc(m, (void **)&m->att, mb * dim * 4) || dmalloc(m, (void **)&m->hb, mb * hid * 4) ||
         dmalloc(m, (void **)&m->g1, mb * hid * 4) || dmalloc(m, (void **)&m->u1, mb * hid * 4) ||
         dmalloc(m, (void **)&m->attn_sync, 2048 * 4) ||
-        dmalloc(m, (void **)&m->attn_xchg, psl_attn_decode2_xchg_bytes((int)f.n_kv_heads, (int)nctx)) || dmalloc(m, (void **)&m->attn_tick, (size_t)f.n_kv_heads * 64 * 4) ||
+        dmalloc(m, (void **)&m->attn_xchg, long_window ? 0 : psl_attn_decode2_xchg_bytes((int)f.n_kv_heads, (int)nctx)) || dmalloc(m, (void **)&m->attn_tick, (size_t)f.n_kv_heads * 64 * 4) ||
         dmalloc(m, (void **)&m->attn_gran, (size_t)(f.n_heads + 2 * f.n_kv_heads) * f.head_size * 8) ||
         dmalloc(m, (void **)&m->scores, mb * f.n_heads * nctx * 4) || dmalloc(m, (void **)&m->logits, mb * f.vocab_size * 4) ||
         dmalloc(m, (void **)&m->rope_table, nctx * f.head_size * 4) ||
@@ -577,6 +587,10 @@ int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **ou
     *out = m;
     return 0;
 }
+
+int ps_hip_model_create(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **out) { return model_create(c, d, out, false); }
+int ps_hip_model_create_long(ps_hip_ctx *c, const ps_model_desc *d, ps_hip_model **out) { return model_create(c, d, out, true); }
+int ps_hip_model_is_long(const ps_hip_model *m) { return m->long_window ? 1 : 0; }
 
 void ps_hip_model_destroy(ps_hip_model *m) {
     if (!m) return;
@@ -697,6 +711,7 @@ static int model_forward(ps_hip_model *m, const int32_t *tokens, int n, const in
             if (graphable) { // capture the same launches (nothing executes); the hint stays a lower bound of n_kv for 1024 positions
                 PS_CHECK(c, sync_stream(m));
                 o.n_kv_host = 0; o.n_kv_hint = pos[0]; // (no host-side n_kv inside a graph: the score grids cover n_ctx)
+                if (m->long_window) o.n_kv_grid = (int)graph_window_end(m, (size_t)pos[0]); // (... or, at a long window, the positions this capture stays valid for)
                 (void)graph_capture(m, g, (size_t)pos[0], [&] { return enqueue_forward(m, 1, o); }); // (a failure: stay eager)
             }
         }
@@ -868,22 +883,34 @@ static int decode_run(ps_hip_model *m, int32_t token, int steps, const ps_sample
         PS_CHECK(c, hipMemcpyAsync(m->tokens_dev, &token, 4, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, c->stream, m->state, (int)position, 1, 0);
         PS_CHECK(c, sync_stream(m));
-        int s = 0;
-        graph_drop_if_stale(g, position);
-        if ((m->mode & 1) == 0 && !g.exec) {
-            // first step runs eagerly (also performs every one-time hipFuncSetAttribute), then the identical
-            // launch sequence is captured; capture itself executes nothing
-            if (int rc = enqueue_forward(m, 1, step)) return rc;
-            PS_CHECK(c, sync_stream(m));
-            s = 1;
-            if (!graph_capture(m, g, position, [&] { return enqueue_forward(m, 1, step); })) { c->err.insert(0, w + "graph capture failed: "); return 2; }
-        }
-        for (; s < steps; s++) {
-            if ((m->mode & 1) == 0) {
-                PS_CHECK(c, hipGraphLaunch(g.exec, c->stream));
-            } else {
-                if (int rc = enqueue_forward(m, 1, step)) return rc;
+        // One loop for both kinds of model.  A regular model looks at its capture once per call (the hint it carries is a prefetch hint: stale costs time, never
+        // results) and replays it to the end.  A long-window model's capture sizes its score grid for the end of its validity window (graph_window_end), so the
+        // run is split there: the step at the boundary runs eagerly, the next window is captured, the replay goes on; its eager steps get the grid of their own position
+        // (Eager mode, bit 0, no longer looks at the capture at all -- it used to drop a stale one on the way in.  Nothing replays it in that mode, and the next call
+        // in mode 0 drops it at s == 0 as before.)
+        const bool lw = m->long_window;
+        for (int s = 0; s < steps;) {
+            const size_t pos = position + (size_t)s;
+            fwd_opts so = step;
+            if (lw) so.n_kv_grid = (int)pos + 1;
+            if (m->mode & 1) {
+                if (int rc = enqueue_forward(m, 1, so)) return rc;
+                s++;
+                continue;
             }
+            if (lw || s == 0) graph_drop_if_stale(g, pos);
+            if (!g.exec) {
+                // this step runs eagerly (the first one also performs every one-time hipFuncSetAttribute), then the identical launch sequence is captured;
+                // capture itself executes nothing
+                if (int rc = enqueue_forward(m, 1, so)) return rc;
+                PS_CHECK(c, sync_stream(m));
+                s++;
+                if (lw) { so.n_kv_grid = (int)graph_window_end(m, pos); so.n_kv_hint = (int)pos; }
+                if (!graph_capture(m, g, pos, [&] { return enqueue_forward(m, 1, so); })) { c->err.insert(0, w + "graph capture failed: "); return 2; }
+                continue;
+            }
+            const int until = lw ? (int)std::min<size_t>((size_t)steps, g.hint + 1024 - position) : steps; // (lw: pos < g.hint + 1024, at least one step)
+            for (; s < until; s++) PS_CHECK(c, hipGraphLaunch(g.exec, c->stream));
         }
         note_single_token(m);
         PS_CHECK(c, hipMemcpyAsync(out_ids, m->ids_dev, (size_t)steps * 4, hipMemcpyDeviceToHost, c->stream));
@@ -973,6 +1000,7 @@ int ps_hip_model_seq_reserve(ps_hip_model *m, int n_seq) {
     if (int rc = settle_pending(m)) return rc;
     if (n_seq < 1) PS_FAIL(c, "seq_reserve: at least one sequence");
     if (n_seq < (int)m->seqs.size()) PS_FAIL(c, "seq_reserve: the model holds more sequences already (growing only)");
+    if (n_seq > 1 && m->long_window) PS_FAIL(c, "seq_reserve: a long-window model holds one sequence (the batched step's kernels keep their soft-max rows in LDS)");
     if (n_seq > 1 && (m->mode & 8)) PS_FAIL(c, "seq_reserve: the fp16-KV decode mode (mode bit 3) mirrors one cache; it does not combine with sequences");
     return seq_grow(m, n_seq);
 }
@@ -995,6 +1023,7 @@ static int batch_check(ps_hip_model *m, const int32_t *seq_ids, const int32_t *t
     const std::string w = std::string(who) + ": ";
     const int cap = m->max_batch < PS_SEQ_COLS_MAX ? m->max_batch : PS_SEQ_COLS_MAX;
     if (n < 1 || n > cap) PS_FAIL(c, w + "1 <= n <= min(16, max_batch) sequences per step");
+    if (m->long_window) PS_FAIL(c, w + "not on a long-window model (the batched step's kernels keep their soft-max rows in LDS)");
     if (m->mode & 8) PS_FAIL(c, w + "the fp16-KV decode mode (mode bit 3) is not available for batched steps");
     if (!seq_ids || !tokens) PS_FAIL(c, w + "null argument");
     for (int i = 0; i < n; i++) {
@@ -1170,9 +1199,10 @@ int ps_hip_model_bench_matmul(ps_hip_model *m, int reps, int which, int bs, doub
 }
 
 int ps_hip_model_set_mode(ps_hip_model *m, int mode) {
-    mode |= mode_env_or();
+    mode |= m->long_window ? mode_env_or() & ~8 : mode_env_or(); // (a long-window model has no fp16-KV mode: the A/B variable does not ask it for one)
     if (mode & 64) { m->attn1_disabled = false; mode &= ~64; } // explicit re-arm of the one-launch attention after a time-out
     if (m->attn1_disabled) mode |= 16;                         // sticky: a later set_mode without bit 4 does not bring the form that timed out back
+    if ((mode & 8) && m->long_window) { m->ctx->err = "set_mode: the fp16-KV decode mode (mode bit 3) is not available on a long-window model"; return 2; }
     if ((mode & 8) && m->seqs.size() > 1) { m->ctx->err = "set_mode: the fp16-KV decode mode mirrors one cache; it does not combine with sequences (seq_reserve)"; return 2; }
     if ((mode & 8) && m->k16.empty()) { // fp16 mirrors of the caches: filled from now on, so the cache must be empty
         if (m->cur().position != 0) { m->ctx->err = "set_mode: the fp16-KV decode mode must be switched on while the cache is empty"; return 2; }

@@ -62,6 +62,11 @@ size_t psl_attn_decode2_xchg_bytes(int n_kv_heads, int n_ctx);
 // layer instead of five; false: not covered, the caller issues the Q / K / V mat-vec (psk_matmul) + psl_attn_decode2
 bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, const psl_attn_args &a);
 size_t psl_attn_softmax_pv_lds(const psl_attn_args &a); // dynamic LDS bytes (grows with n_ctx)
+void psl_attn_pv_mfma(hipStream_t st, const psl_attn_args &a, int bs); // bs >= 8: V.p on the matrix cores over the probabilities in a.scores (what psl_attn_softmax_pv launches behind its soft-max)
+// long-window models (k_attn_long.hip): soft-max with the rows in device memory + V.p, behind psl_attn_scores; any n_ctx up to PS_HIP_LONG_CTX_MAX
+void psl_attn_long_softmax_pv(hipStream_t st, const psl_attn_args &a, int bs);
+void psl_softmax_long_ext(hipStream_t st, const ps_tensor *dst, const ps_tensor *src, const float *mask, float scale); // softmax_ext rows above the LDS-resident kernel's cap
+int psl_attn_long_set_tile(int positions); // ps_hip_debug_set(13, v)
 
 // ---- batched decode: one token per SEQUENCE, each sequence on a KV cache of its own (ps_hip_model_decode_batch)
 // Device table of a batched step.  col[i] = (sequence, position) of batch column i: the token goes to cache slot `pos` of that sequence (its RoPE position too)

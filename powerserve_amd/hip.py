@@ -36,7 +36,10 @@ EXPORTS = [
     "ps_hip_sample_covered", "ps_hip_sample", "ps_hip_model_decode_sampled", "ps_hip_sample_counters", "ps_hip_last_sample_kernels",
     "ps_hip_model_seq_reserve", "ps_hip_model_seq_count", "ps_hip_model_seq_position", "ps_hip_model_seq_select", "ps_hip_model_decode_batch", "ps_hip_model_decode_batch_greedy",
     "ps_hip_score_rows", "ps_hip_model_score", "ps_hip_score_counters",
+    "ps_hip_model_create_long", "ps_hip_model_is_long", "ps_hip_softmax_long_counters",
 ]
+LONG_CTX_MAX = 131072  # PS_HIP_LONG_CTX_MAX (include/ps_hip.h)
+DEBUG_LONG_PV_TILE, DEBUG_LONG_EPS_SHIFT = 13, 14  # ps_hip_debug_set keys: attn_pv_long_kernel's tile (positions), the long soft-max certificate's eps x 2^value
 SAMPLE_K_MAX, SAMPLE_WINDOW_MAX = 256, 1024  # PS_SAMPLE_K_MAX, PS_SAMPLE_WINDOW_MAX (include/ps_hip.h)
 
 
@@ -177,6 +180,8 @@ def lib() -> C.CDLL:
         "ps_hip_last_sample_kernels": (C.c_char_p, []),
         "ps_hip_score_rows": (i32, [vp, vp, i32, i64, i32, vp, vp]), "ps_hip_model_score": (i32, [vp, vp, vp, i32, i32, vp]),
         "ps_hip_score_counters": (None, [vp, i32]),
+        "ps_hip_model_create_long": (i32, [vp, C.POINTER(ModelDesc), C.POINTER(vp)]), "ps_hip_model_is_long": (i32, [vp]),
+        "ps_hip_softmax_long_counters": (None, [vp, i32]),
         "ps_hip_debug_f16_gemm": (i32, [vp, i32, C.c_int64, C.c_int64, i32, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -315,7 +320,8 @@ class Weight:
 class Model:
     """ps_hip_model over a PowerServe model directory (model.json + ggml/weights.gguf)."""
 
-    def __init__(self, ctx: Ctx, model_dir: str, max_batch: int = 128, n_ctx: int | None = None):
+    def __init__(self, ctx: Ctx, model_dir: str, max_batch: int = 128, n_ctx: int | None = None, long_window: bool = False):
+        """long_window: a long-window model (ps_hip_model_create_long): any n_ctx that is a multiple of 4 up to LONG_CTX_MAX, attention rows in device memory"""
         self.ctx = ctx
         with open(os.path.join(model_dir, "model.json")) as f:
             mj = json.load(f)
@@ -362,7 +368,16 @@ class Model:
                 self._keep.append(a)
                 setattr(d, field, a)
         h = C.c_void_p()
-        ctx.check(ctx.L.ps_hip_model_create(ctx.h, C.byref(d), C.byref(h)))
+        create = ctx.L.ps_hip_model_create_long if long_window else ctx.L.ps_hip_model_create
+        try:
+            ctx.check(create(ctx.h, C.byref(d), C.byref(h)))
+        except PSHipError:  # (a refused window, no device memory: the weights uploaded above go back -- they used to stay allocated until the process ended)
+            self.h = None  # (close() is a no-op on a model that was never created)
+            for w in self.weights.values():
+                w.free()
+            for a in self.f32.values():
+                a.free()
+            raise
         self.h, self.max_batch = h, max_batch
 
     def close(self):
@@ -373,6 +388,10 @@ class Model:
                 w.free()
             for a in self.f32.values():
                 a.free()
+
+    @property
+    def is_long(self) -> bool:
+        return bool(self.ctx.L.ps_hip_model_is_long(self.h))
 
     @property
     def position(self) -> int:
@@ -593,3 +612,10 @@ def score_counters(reset: bool = False):
     out = (C.c_uint64 * 3)()
     lib().ps_hip_score_counters(out, int(reset))
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def softmax_long_counters(reset: bool = False):
+    """(rows soft-maxed by the long-window kernels, of them through the sequential sum) since the last reset, process-wide"""
+    out = (C.c_uint64 * 2)()
+    lib().ps_hip_softmax_long_counters(out, int(reset))
+    return int(out[0]), int(out[1])

@@ -17,7 +17,8 @@ EXPORTS = ["psh_last_error", "psh_model_load", "psh_model_free", "psh_model_set_
            "psh_model_set_device_sampling", "psh_sampler_engine_state", "psh_sampler_device_state", "psh_sampler_is_standard", "psh_sampler_append_noop", "psh_model_generate_with_chain",
            "psh_debug_mt_seed", "psh_debug_mt_next", "psh_debug_discrete", "psh_debug_partial_sort", "psh_debug_chain", "psh_debug_std_mt",
            "psh_debug_std_mt_seed", "psh_debug_std_discrete", "psh_debug_std_partial_sort",
-           "psh_model_score", "psh_ppl_create", "psh_ppl_destroy", "psh_ppl_add", "psh_ppl_current", "psh_ppl_logit_sum", "psh_ppl_n_tokens", "psh_debug_score_row", "psh_debug_score_certify"]
+           "psh_model_score", "psh_ppl_create", "psh_ppl_destroy", "psh_ppl_add", "psh_ppl_current", "psh_ppl_logit_sum", "psh_ppl_n_tokens", "psh_debug_score_row", "psh_debug_score_certify",
+           "psh_model_load_long", "psh_debug_softmax_long_sum"]
 _LIB = None
 
 
@@ -101,6 +102,10 @@ def lib() -> C.CDLL:
         L.psh_debug_score_row.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.psh_debug_score_certify.restype = C.c_uint32
         L.psh_debug_score_certify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.psh_model_load_long.restype = C.c_void_p
+        L.psh_model_load_long.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.psh_debug_softmax_long_sum.restype = C.c_int
+        L.psh_debug_softmax_long_sum.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -127,9 +132,12 @@ class HostError(RuntimeError):
 class HostModel:
     """load_model(dir) + Model::forward / generate through the C++ facade."""
 
-    def __init__(self, model_dir: str, device: int = 0, max_batch: int = 128, n_ctx: int = 0):
+    def __init__(self, model_dir: str, device: int = 0, max_batch: int = 128, n_ctx: int = 0, long_window: bool = False):
         self.L = lib()
-        self.h = self.L.psh_model_load(model_dir.encode(), device, max_batch, n_ctx)
+        if long_window:  # load_model(..., long_window = true): any n_ctx up to 131072, attention rows in device memory (include/ps_hip.h ps_hip_model_create_long)
+            self.h = self.L.psh_model_load_long(model_dir.encode(), device, max_batch, n_ctx, 1)
+        else:
+            self.h = self.L.psh_model_load(model_dir.encode(), device, max_batch, n_ctx)
         if not self.h:
             raise HostError(self.L.psh_last_error().decode())
         self.vocab = self.L.psh_model_vocab(self.h)
@@ -565,3 +573,12 @@ def score_row_certify(x: np.ndarray, t: int, shift: int = 0):
     p, m, a = C.c_float(), C.c_float(), C.c_int32()
     fl = lib().psh_debug_score_certify(x.ctypes.data, x.size, int(t), int(shift), C.byref(p), C.byref(m), C.byref(a))
     return int(fl), np.float32(p.value), np.float32(m.value), int(a.value)
+
+
+def softmax_long_sum(e: np.ndarray, lanes: int = 1024, shift: int = 0):
+    """The long soft-max's row sum on the CPU (csrc/ps_softmax_long_dev.h) for a row of numerators e: (certified, inv_fast, inv_seq) -- (float)(1 / S) of a
+    `lanes`-lane order, the reference's factor from its sequential sum, and whether the certificate (eps x 2^shift) closed on S"""
+    e = np.ascontiguousarray(e, dtype=np.float32)
+    a, b = C.c_float(), C.c_float()
+    ok = lib().psh_debug_softmax_long_sum(e.ctypes.data, e.size, int(lanes), int(shift), C.byref(a), C.byref(b))
+    return bool(ok), np.float32(a.value), np.float32(b.value)

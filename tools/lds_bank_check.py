@@ -45,3 +45,20 @@ for name, f in (("piece ^ (row & 7) (first version: built for '8 consecutive lan
     print(f"  {name}: ds_read_b128 {worst} pass(es)")
 print("  64-byte rows (32-k blocks: the four-wave experiment), piece ^ (row / 4 % 4): ds_read_b128 "
       f"{max(passes(lambda l, ks=ks: (l & 31) * 64 + (((2 * ks + (l >> 5)) ^ (((l & 31) >> 2) & 3)) << 4), RD, 64) for ks in range(2))} pass(es)")
+
+print("long-window V.p tile (k_attn_long.hip attn_pv_long_kernel: rows of STR = round_up(T, 64) + 32 floats; a wave = chains c = l & 31 of channels dl = l >> 5 and dl + 1 of one head):")
+
+
+def passes_b32(addr):  # ds_read_b32: all 64 lanes over 64 banks; the same address is a broadcast
+    per_bank = {}
+    for l in range(64):
+        per_bank.setdefault((addr(l) >> 2) % 64, set()).add(addr(l))
+    return max(len(v) for v in per_bank.values())
+
+
+for T in (32, 64, 96, 2048):
+    STR = ((T + 63) & ~63) + 32
+    v = max(passes_b32(lambda l, j=j: ((l >> 5) * STR + j + (l & 31)) * 4) for j in range(0, T, 32))
+    p = passes_b32(lambda l: (4 * STR + (l & 31)) * 4)
+    park = max(passes(lambda l, w=w: (((64 * w + l) // (T // 4)) * STR + ((64 * w + l) % (T // 4)) * 4) * 4, WR, 32) for w in range(16))
+    print(f"  T = {T:4d} (STR {STR}): V ds_read_b32 {v} pass(es), p ds_read_b32 {p} pass(es), tile park ds_write_b128 {park} pass(es)")
