@@ -322,6 +322,26 @@ int ps_hip_model_seq_select(ps_hip_model *m, int seq);
 int ps_hip_model_decode_batch(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int lm_head, int32_t *argmax_host);
 /* `steps` such steps, each column fed its own arg-max, without a host round trip per step.  out_ids HOST int32[steps][n]. */
 int ps_hip_model_decode_batch_greedy(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int steps, int32_t *out_ids);
+/* Fork (DESIGN.md "Fork, save and restore").  A forward only writes slots at or behind the position, so a prefix of one sequence is, bit for bit, a valid prefix of
+ * another: one prefill serves every conversation behind the same system prompt and every one of n / best_of completions.
+ * dst sequences get slots [0, n_tokens) of src's K / V in every layer; their position becomes n_tokens, all their slots visible.  Afterwards each destination behaves in
+ * every entry point (single-sequence calls after seq_select, decode_batch, decode_batch_greedy, forward_tree, score, the captured decode steps) bit for bit like a
+ * sequence that had src's history of n_tokens tokens.  One launch for all layers and up to 15 destinations (csrc/k_seqcopy.hip); src is not modified; slots >= n_tokens
+ * of a destination keep their bytes; n_tokens == 0 empties the destinations; src or a destination may be the current sequence.
+ * rc 2, nothing changed: n_dst outside 1 .. seq_count - 1, an id out of range, a destination equal to src or listed twice, n_tokens > src's position, src with hidden
+ * slots (kv_mask).  (A long-window or fp16-KV model holds one sequence: the id checks refuse it.) */
+int ps_hip_model_seq_fork(ps_hip_model *m, int src_seq, const int32_t *dst_seqs, int n_dst, size_t n_tokens);
+/* Save / restore.  The state of a sequence's first n_tokens slots as a host blob that does not depend on n_ctx: a 64-byte little-endian header ("PSKV", version 1,
+ * n_layers, kv_dim, head_size, n_tokens u64, the writer's ps_hip_build_contract(), zeros; csrc/ps_kv_state.h), then per layer K [n_tokens][kv_dim] f32 and
+ * V [kv_dim][n_tokens] f32: seq_state_bytes = 64 + n_layers * 2 * n_tokens * kv_dim * 4.  A blob restores into a sequence of any model with the same n_layers,
+ * kv_dim, head_size and build -- another window, another max_batch, a long-window model.  THE BLOB DOES NOT IDENTIFY THE WEIGHTS: keeping a state with the model
+ * it was computed by is the caller's responsibility.
+ * seq_export refuses (rc 2): an id out of range, n_tokens > the sequence's position, hidden slots, bytes < seq_state_bytes(n_tokens), mode bit 3.
+ * seq_import sets the position to the header's n_tokens with all slots visible; slots beyond stay as they are.  It refuses (rc 2, nothing changed): an id out of range,
+ * a bad magic, version or contract flag, another n_layers / kv_dim / head_size, n_tokens > n_ctx, bytes != what the header implies, mode bit 3. */
+size_t ps_hip_model_seq_state_bytes(const ps_hip_model *m, size_t n_tokens);
+int ps_hip_model_seq_export(ps_hip_model *m, int seq, size_t n_tokens, void *host_buf, size_t bytes);
+int ps_hip_model_seq_import(ps_hip_model *m, int seq, const void *host_buf, size_t bytes);
 
 const float *ps_hip_model_logits(const ps_hip_model *m); /* device [max_batch][vocab] */
 /* Arg-max ids of the most recent forward with lm_head (first maximum per token, what greedy_sample / TopK(1) returns: src/sampler/prob_array.cpp:65-67,

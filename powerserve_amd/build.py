@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
-SOURCES = ["api.hip", "model.hip", "matmul.hip", "k_quant.hip", "k_gemv.hip", "k_gemv4.hip", "k_qkvattn.hip", "k_gemvb.hip", "k_gemvk.hip", "k_gemm4k.hip", "k_gemv6.hip", "k_gemvh.hip", "k_ops.hip", "k_attn.hip", "k_attn_long.hip", "perf16.hip", "k_sample.hip", "k_score.hip"]
+SOURCES = ["api.hip", "model.hip", "matmul.hip", "k_quant.hip", "k_gemv.hip", "k_gemv4.hip", "k_qkvattn.hip", "k_gemvb.hip", "k_gemvk.hip", "k_gemm4k.hip", "k_gemv6.hip", "k_gemvh.hip", "k_ops.hip", "k_attn.hip", "k_attn_long.hip", "perf16.hip", "k_sample.hip", "k_score.hip", "k_seqcopy.hip"]
 # -ffp-contract=off: the parity contract needs every fp32 op to round where the reference's C source rounds;
 # fused multiply-adds are written explicitly (__fmaf_rn) where the reference uses FMA intrinsics.
 # -fno-slp-vectorize (NOSLP files only): hipcc's SLP vectoriser packs adjacent scalar fp32 operations into v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32.  On
@@ -114,6 +114,7 @@ def build_host(force: bool = False, verbose: bool = True) -> str:
     so = os.path.join(LIBDIR, "libps_host.so")
     srcs = [os.path.join(hdir, f) for f in HOST_SOURCES]
     deps = srcs + [os.path.join(hdir, f) for f in os.listdir(hdir) if f.endswith(".hpp")] + [os.path.join(HERE, "..", "include", "ps_hip.h")]
+    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]  # (the headers shared with the device side: ps_score_dev.h, ps_kv_state.h ...)
     if not force and os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps):
         return so
     if verbose:

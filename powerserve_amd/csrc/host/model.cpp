@@ -1,4 +1,5 @@
 #include "model.hpp"
+#include "../ps_kv_state.h"
 
 #include <cmath>
 #include <cstring>
@@ -282,6 +283,22 @@ auto Model::decode_batch(const std::vector<int> &seq_ids, const std::vector<Toke
         POWERSERVE_ABORT(std::string("decode_batch: ") + ps_hip_last_error(be.m_ctx));
     return std::vector<Token>(ids.begin(), ids.end());
 }
+void Model::fork_sequence(size_t src, const std::vector<int> &dsts, size_t n_tokens) {
+    POWERSERVE_ASSERT(!dsts.empty());
+    auto &be = backend();
+    std::vector<int32_t> d(dsts.begin(), dsts.end());
+    if (ps_hip_model_seq_fork(be.m_model, (int)src, d.data(), (int)d.size(), n_tokens)) POWERSERVE_ABORT(std::string("fork_sequence: ") + ps_hip_last_error(be.m_ctx));
+}
+auto Model::export_sequence(size_t seq, size_t n_tokens) -> std::vector<uint8_t> {
+    auto &be = backend();
+    std::vector<uint8_t> blob(ps_hip_model_seq_state_bytes(be.m_model, n_tokens));
+    if (ps_hip_model_seq_export(be.m_model, (int)seq, n_tokens, blob.data(), blob.size())) POWERSERVE_ABORT(std::string("export_sequence: ") + ps_hip_last_error(be.m_ctx));
+    return blob;
+}
+void Model::import_sequence(size_t seq, const void *blob, size_t bytes) {
+    auto &be = backend();
+    if (ps_hip_model_seq_import(be.m_model, (int)seq, blob, bytes)) POWERSERVE_ABORT(std::string("import_sequence: ") + ps_hip_last_error(be.m_ctx));
+}
 
 void Model::prefill(const std::vector<Token> &tokens, size_t batch_size) {
     if (tokens.empty()) return;
@@ -460,6 +477,35 @@ int psh_model_decode_batch(void *h, const int32_t *seq_ids, const int32_t *token
         for (int i = 0; i < n; i++) ids_out[i] = r[i];
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int psh_model_seq_fork(void *h, int src, const int32_t *dsts, int n_dst, int64_t n_tokens) { // Model::fork_sequence
+    try { ((psh_model *)h)->model->fork_sequence((size_t)src, std::vector<int>(dsts, dsts + n_dst), (size_t)n_tokens); return 0; } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// Model::export_sequence into the caller's buffer of `cap` bytes; returns the blob's length (out == NULL: nothing is copied, the length only), -1 on failure
+int64_t psh_model_seq_export(void *h, int seq, int64_t n_tokens, uint8_t *out, int64_t cap) {
+    try {
+        auto m = (psh_model *)h;
+        const size_t need = ps_hip_model_seq_state_bytes(m->model->backend().m_model, (size_t)n_tokens);
+        if (!out) return (int64_t)need;
+        POWERSERVE_ASSERT((size_t)cap >= need, "export_sequence: buffer too small");
+        auto blob = m->model->export_sequence((size_t)seq, (size_t)n_tokens);
+        memcpy(out, blob.data(), blob.size());
+        return (int64_t)blob.size();
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+int psh_model_seq_import(void *h, int seq, const uint8_t *blob, int64_t bytes) { // Model::import_sequence
+    try { ((psh_model *)h)->model->import_sequence((size_t)seq, blob, (size_t)bytes); return 0; } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// CPU build of the state header's check (csrc/ps_kv_state.h, the same source csrc/model.hip compiles): 0 = a model of this shape and build takes the blob (*n_tokens =
+// its length), 2 = refused (psh_last_error says why).  Only the header is read.
+int psh_debug_kv_state_check(const void *blob, uint64_t bytes, uint32_t n_layers, uint32_t kv_dim, uint32_t head_size, uint64_t n_ctx, uint32_t contract, uint64_t *n_tokens) {
+    const char *why = ps_kv_state_check(blob, bytes, n_layers, kv_dim, head_size, n_ctx, contract, n_tokens);
+    if (why) { g_err = why; return 2; }
+    return 0;
+}
+// ... and of its writer: 64 bytes at out
+void psh_debug_kv_state_header(void *out, uint32_t n_layers, uint32_t kv_dim, uint32_t head_size, uint64_t n_tokens, uint32_t contract) {
+    ps_kv_state_write_header(out, n_layers, kv_dim, head_size, n_tokens, contract);
 }
 int psh_model_prefill(void *h, const int32_t *tokens, int n, int batch_size) { // ModelTokenIterator's prefill loop
     try {

@@ -94,6 +94,13 @@ struct Model {
     // one greedy step: tokens[i] goes to sequence seq_ids[i] at that sequence's position and advances it; returns the arg-max id per column.
     // logits_out (optional): host [n][vocab] logits of the columns
     auto decode_batch(const std::vector<int> &seq_ids, const std::vector<Token> &tokens, float *logits_out = nullptr) -> std::vector<Token>;
+    // fork: the first n_tokens slots of sequence src become the history of every sequence of dsts (ps_hip_model_seq_fork: one launch, src untouched) -- one prefill
+    // of a shared system prompt, or of the prompt of n / best_of completions (app/server/openai_api.hpp:122-123), serves them all
+    void fork_sequence(size_t src, const std::vector<int> &dsts, size_t n_tokens);
+    // save / restore: a sequence's first n_tokens slots as a host blob independent of n_ctx (ps_hip_model_seq_export / _import; csrc/ps_kv_state.h).  The blob
+    // does not identify the weights.  import_sequence takes a blob of any compatible model (same layers, kv_dim, head_size and build)
+    auto export_sequence(size_t seq, size_t n_tokens) -> std::vector<uint8_t>;
+    void import_sequence(size_t seq, const void *blob, size_t bytes);
 
     hip::HIPBackend &backend() { return *m_platform->hip_backends[m_config->model_id]; }
 

@@ -13,6 +13,7 @@
 #include "ps_internal.h"
 #include <algorithm>
 #include "ps_ops.h"
+#include "ps_kv_state.h"
 
 #include <cstdio>
 #include <cstring>
@@ -1096,6 +1097,90 @@ int ps_hip_model_decode_batch_greedy(ps_hip_model *m, const int32_t *seq_ids, co
     PS_CHECK(c, hipMemcpyAsync(out_ids, m->seq_ids_dev, (size_t)steps * n * 4, hipMemcpyDeviceToHost, c->stream));
     PS_CHECK(c, sync_stream(m));
     batch_advance(m, seq_ids, n, (size_t)steps);
+    return 0;
+}
+
+// ---- fork / save / restore (include/ps_hip.h "Sequences").  A forward only ever writes slots at or behind the position, so the first n slots of a
+// sequence are, bit for bit, a valid history of n tokens for any other cache of the same shape.
+// the sequence stands behind n tokens, every slot visible (what kv_truncate leaves); the captured steps hold cache pointers and no position: they stay
+static void seq_set_history(ps_hip_model *m, ps_hip_model::seq_state &s, size_t n) {
+    s.position = n;
+    if (!s.n_hidden) return;
+    std::fill(s.kv_vis_host.begin(), s.kv_vis_host.end(), (uint8_t)1);
+    s.n_hidden = 0;
+    (void)hipMemsetAsync(s.kv_vis_dev, 1, m->cfg.seq_len, m->ctx->stream);
+}
+int ps_hip_model_seq_fork(ps_hip_model *m, int src, const int32_t *dst, int n_dst, size_t n_tokens) {
+    ps_hip_ctx *c = m->ctx;
+    if (int rc = settle_pending(m)) return rc;
+    const int n_seq = (int)m->seqs.size();
+    if (n_dst < 1 || n_dst > n_seq - 1) PS_FAIL(c, "seq_fork: 1 <= n_dst <= seq_count - 1 destinations");
+    if (!dst) PS_FAIL(c, "seq_fork: null argument");
+    if (src < 0 || src >= n_seq) PS_FAIL(c, "seq_fork: no such sequence: " + std::to_string(src));
+    for (int i = 0; i < n_dst; i++) {
+        if (dst[i] < 0 || dst[i] >= n_seq) PS_FAIL(c, "seq_fork: no such sequence: " + std::to_string(dst[i]));
+        if (dst[i] == src) PS_FAIL(c, "seq_fork: sequence " + std::to_string(src) + " is the source and a destination");
+        for (int j = 0; j < i; j++) if (dst[j] == dst[i]) PS_FAIL(c, "seq_fork: sequence " + std::to_string(dst[i]) + " appears twice");
+    }
+    if (n_tokens > m->seqs[src].position) PS_FAIL(c, "seq_fork: more tokens than the source holds");
+    if (m->seqs[src].n_hidden) PS_FAIL(c, "seq_fork: the source has hidden KV slots (kv_mask); unmask first");
+    PS_CHECK(c, hipSetDevice(c->device));
+    psl_fork_args a{};
+    a.kv = m->seq_kv_dev; // (two sequences exist: seq_grow made the table)
+    a.n_layers = (int)m->cfg.n_layers; a.kv_dim = (int)m->cfg.kv_dim; a.n_ctx = (int)m->cfg.seq_len; a.n_tokens = (int)n_tokens; a.src = src;
+    for (int i = 0; n_tokens && i < n_dst; i += PS_FORK_DST_MAX) {
+        a.n_dst = std::min(n_dst - i, PS_FORK_DST_MAX);
+        std::copy(dst + i, dst + i + a.n_dst, a.dst);
+        psl_seq_fork(c->stream, a);
+    }
+    PS_CHECK(c, hipGetLastError());
+    for (int i = 0; i < n_dst; i++) seq_set_history(m, m->seqs[dst[i]], n_tokens);
+    PS_CHECK(c, sync_stream(m));
+    return 0;
+}
+
+size_t ps_hip_model_seq_state_bytes(const ps_hip_model *m, size_t n_tokens) { return ps_kv_state_bytes(m->cfg.n_layers, m->cfg.kv_dim, n_tokens); }
+// K is a contiguous prefix, V a pitched copy (rows of n_tokens floats at pitch n_ctx); all on the ctx stream, one wait at the end
+static int seq_state_copy(ps_hip_model *m, ps_hip_model::seq_state &s, uint8_t *host, size_t n, bool to_host) {
+    ps_hip_ctx *c = m->ctx;
+    const size_t kvd = m->cfg.kv_dim, plane = ps_kv_state_plane_bytes(m->cfg.kv_dim, n), pitch = (size_t)m->cfg.seq_len * 4;
+    PS_CHECK(c, hipSetDevice(c->device));
+    uint8_t *p = host + PS_KV_STATE_HEADER;
+    for (uint32_t L = 0; n && L < m->cfg.n_layers; L++, p += 2 * plane) {
+        if (to_host) {
+            PS_CHECK(c, hipMemcpyAsync(p, s.k_cache[L], plane, hipMemcpyDeviceToHost, c->stream));
+            PS_CHECK(c, hipMemcpy2DAsync(p + plane, n * 4, s.v_cache[L], pitch, n * 4, kvd, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            PS_CHECK(c, hipMemcpyAsync(s.k_cache[L], p, plane, hipMemcpyHostToDevice, c->stream));
+            PS_CHECK(c, hipMemcpy2DAsync(s.v_cache[L], pitch, p + plane, n * 4, n * 4, kvd, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    PS_CHECK(c, sync_stream(m));
+    return 0;
+}
+int ps_hip_model_seq_export(ps_hip_model *m, int seq, size_t n_tokens, void *host_buf, size_t bytes) {
+    ps_hip_ctx *c = m->ctx;
+    if (int rc = settle_pending(m)) return rc;
+    if (seq < 0 || seq >= (int)m->seqs.size()) PS_FAIL(c, "seq_export: no such sequence");
+    if (m->mode & 8) PS_FAIL(c, "seq_export: not in the fp16-KV decode mode (mode bit 3: the single-token attention reads the fp16 mirrors, which a state does not carry)");
+    ps_hip_model::seq_state &s = m->seqs[seq];
+    if (n_tokens > s.position) PS_FAIL(c, "seq_export: more tokens than the sequence holds");
+    if (s.n_hidden) PS_FAIL(c, "seq_export: the sequence has hidden KV slots (kv_mask); unmask first");
+    if (!host_buf || bytes < ps_hip_model_seq_state_bytes(m, n_tokens)) PS_FAIL(c, "seq_export: buffer smaller than ps_hip_model_seq_state_bytes");
+    ps_kv_state_write_header(host_buf, m->cfg.n_layers, m->cfg.kv_dim, m->cfg.head_size, n_tokens, (uint32_t)ps_hip_build_contract());
+    return seq_state_copy(m, s, (uint8_t *)host_buf, n_tokens, true);
+}
+int ps_hip_model_seq_import(ps_hip_model *m, int seq, const void *host_buf, size_t bytes) {
+    ps_hip_ctx *c = m->ctx;
+    if (int rc = settle_pending(m)) return rc;
+    if (seq < 0 || seq >= (int)m->seqs.size()) PS_FAIL(c, "seq_import: no such sequence");
+    if (m->mode & 8) PS_FAIL(c, "seq_import: not in the fp16-KV decode mode (mode bit 3: the fp16 mirrors would not follow)");
+    uint64_t n = 0;
+    if (const char *why = ps_kv_state_check(host_buf, bytes, m->cfg.n_layers, m->cfg.kv_dim, m->cfg.head_size, m->cfg.seq_len, (uint32_t)ps_hip_build_contract(), &n))
+        PS_FAIL(c, std::string("seq_import: ") + why);
+    ps_hip_model::seq_state &s = m->seqs[seq];
+    if (int rc = seq_state_copy(m, s, (uint8_t *)const_cast<void *>(host_buf), (size_t)n, false)) return rc;
+    seq_set_history(m, s, (size_t)n);
     return 0;
 }
 

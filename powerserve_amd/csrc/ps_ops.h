@@ -90,6 +90,16 @@ void psl_rope_append_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs
 void psl_attn_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs_args &s, int n);
 // bookkeeping of a greedy batched step: token[i] = argmax[i], ids[n_out * n + i] = argmax[i], col[i].pos++, n_out++
 void psl_seqs_advance(hipStream_t st, ps_seq_table *tab, const int32_t *argmax, int32_t *tokens, int32_t *ids, int n);
+// fork (k_seqcopy.hip): slots [0, n_tokens) of sequence `src`, K and V of every layer, into the n_dst sequences dst[] in one launch; kv as psl_seqs_args::kv.
+// More destinations than PS_FORK_DST_MAX take another launch (ps_hip_model_seq_fork).
+#define PS_FORK_DST_MAX 15
+struct psl_fork_args {
+    float *const *kv;
+    int n_layers, kv_dim, n_ctx, n_tokens; // n_tokens >= 1
+    int src, n_dst;
+    int dst[PS_FORK_DST_MAX];
+};
+void psl_seq_fork(hipStream_t st, const psl_fork_args &a);
 // two-stage arg-max (64 partials per row).  With state != NULL the final stage also does the greedy-decode
 // bookkeeping: token[0] = id, ids[state->n_out++] = id, state->pos0++.
 void psl_argmax2(hipStream_t st, const float *src, int64_t n, int64_t rows, int32_t *out, float *part_v, int *part_i,

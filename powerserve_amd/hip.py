@@ -37,6 +37,7 @@ EXPORTS = [
     "ps_hip_model_seq_reserve", "ps_hip_model_seq_count", "ps_hip_model_seq_position", "ps_hip_model_seq_select", "ps_hip_model_decode_batch", "ps_hip_model_decode_batch_greedy",
     "ps_hip_score_rows", "ps_hip_model_score", "ps_hip_score_counters",
     "ps_hip_model_create_long", "ps_hip_model_is_long", "ps_hip_softmax_long_counters",
+    "ps_hip_model_seq_fork", "ps_hip_model_seq_state_bytes", "ps_hip_model_seq_export", "ps_hip_model_seq_import",
 ]
 LONG_CTX_MAX = 131072  # PS_HIP_LONG_CTX_MAX (include/ps_hip.h)
 DEBUG_LONG_PV_TILE, DEBUG_LONG_EPS_SHIFT = 13, 14  # ps_hip_debug_set keys: attn_pv_long_kernel's tile (positions), the long soft-max certificate's eps x 2^value
@@ -182,6 +183,8 @@ def lib() -> C.CDLL:
         "ps_hip_score_counters": (None, [vp, i32]),
         "ps_hip_model_create_long": (i32, [vp, C.POINTER(ModelDesc), C.POINTER(vp)]), "ps_hip_model_is_long": (i32, [vp]),
         "ps_hip_softmax_long_counters": (None, [vp, i32]),
+        "ps_hip_model_seq_fork": (i32, [vp, i32, vp, i32, sz]), "ps_hip_model_seq_state_bytes": (sz, [vp, sz]),
+        "ps_hip_model_seq_export": (i32, [vp, i32, sz, vp, sz]), "ps_hip_model_seq_import": (i32, [vp, i32, vp, sz]),
         "ps_hip_debug_f16_gemm": (i32, [vp, i32, C.c_int64, C.c_int64, i32, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -540,6 +543,28 @@ class Model:
         out = np.empty((int(steps), tokens.size), dtype=np.int32)
         self.ctx.check(self.ctx.L.ps_hip_model_decode_batch_greedy(self.h, _ptr(seq_ids), _ptr(tokens), tokens.size, int(steps), _ptr(out)))
         return out
+
+    # ---- fork / save / restore (include/ps_hip.h ps_hip_model_seq_fork / _export / _import)
+    def seq_fork(self, src: int, dsts, n_tokens: int | None = None):
+        """Slots [0, n_tokens) of sequence src into every sequence of dsts (one launch); n_tokens None: src's whole history."""
+        d = np.ascontiguousarray(dsts, dtype=np.int32).reshape(-1)
+        n = self.seq_position(src) if n_tokens is None else int(n_tokens)
+        self.ctx.check(self.ctx.L.ps_hip_model_seq_fork(self.h, int(src), _ptr(d), d.size, n))
+
+    def seq_state_bytes(self, n_tokens: int) -> int:
+        return self.ctx.L.ps_hip_model_seq_state_bytes(self.h, int(n_tokens))
+
+    def seq_export(self, seq: int, n_tokens: int | None = None) -> np.ndarray:
+        """The first n_tokens slots of a sequence (None: all of it) as a uint8 blob that does not depend on n_ctx.  It does not identify the weights."""
+        n = self.seq_position(seq) if n_tokens is None else int(n_tokens)
+        blob = np.empty(self.seq_state_bytes(n), dtype=np.uint8)
+        self.ctx.check(self.ctx.L.ps_hip_model_seq_export(self.h, int(seq), n, _ptr(blob), blob.nbytes))
+        return blob
+
+    def seq_import(self, seq: int, blob):
+        """Restore a blob of seq_export (this or a compatible model: same layers, kv_dim, head_size and build) into a sequence."""
+        b = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        self.ctx.check(self.ctx.L.ps_hip_model_seq_import(self.h, int(seq), _ptr(b), b.nbytes))
 
     def decode_sampled(self, token: int, steps: int, cfg: SampleCfg, state: SampleState) -> np.ndarray:
         """decode_greedy with the standard sampler chain in place of the arg-max; `state` (engine, window) is advanced in place."""

@@ -18,7 +18,8 @@ EXPORTS = ["psh_last_error", "psh_model_load", "psh_model_free", "psh_model_set_
            "psh_debug_mt_seed", "psh_debug_mt_next", "psh_debug_discrete", "psh_debug_partial_sort", "psh_debug_chain", "psh_debug_std_mt",
            "psh_debug_std_mt_seed", "psh_debug_std_discrete", "psh_debug_std_partial_sort",
            "psh_model_score", "psh_ppl_create", "psh_ppl_destroy", "psh_ppl_add", "psh_ppl_current", "psh_ppl_logit_sum", "psh_ppl_n_tokens", "psh_debug_score_row", "psh_debug_score_certify",
-           "psh_model_load_long", "psh_debug_softmax_long_sum"]
+           "psh_model_load_long", "psh_debug_softmax_long_sum",
+           "psh_model_seq_fork", "psh_model_seq_export", "psh_model_seq_import", "psh_debug_kv_state_check", "psh_debug_kv_state_header"]
 _LIB = None
 
 
@@ -106,6 +107,13 @@ def lib() -> C.CDLL:
         L.psh_model_load_long.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.psh_debug_softmax_long_sum.restype = C.c_int
         L.psh_debug_softmax_long_sum.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.psh_model_seq_fork.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64]
+        L.psh_model_seq_export.restype = C.c_int64
+        L.psh_model_seq_export.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]
+        L.psh_model_seq_import.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+        L.psh_debug_kv_state_check.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
+        L.psh_debug_kv_state_header.restype = None
+        L.psh_debug_kv_state_header.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -233,6 +241,34 @@ class HostModel:
         if self.L.psh_model_decode_batch(self.h, s.ctypes.data, t.ctypes.data, t.size, ids.ctypes.data, lg.ctypes.data if want_logits else None):
             raise HostError(self.L.psh_last_error().decode())
         return (ids, lg) if want_logits else ids
+
+    # ---- fork / save / restore (Model::fork_sequence / export_sequence / import_sequence)
+    def fork_sequence(self, src: int, dsts, n_tokens: int | None = None):
+        """The first n_tokens slots of sequence src (None: all it holds) become the history of every sequence of dsts."""
+        d = np.ascontiguousarray(dsts, dtype=np.int32).reshape(-1)
+        if d.size == 0:
+            raise ValueError("fork_sequence: at least one destination")
+        if int(src) in d.tolist():
+            raise ValueError("fork_sequence: the source is among the destinations")
+        n = self.sequence_position(src) if n_tokens is None else int(n_tokens)
+        if self.L.psh_model_seq_fork(self.h, int(src), d.ctypes.data, d.size, n):
+            raise HostError(self.L.psh_last_error().decode())
+
+    def export_sequence(self, seq: int, n_tokens: int | None = None) -> np.ndarray:
+        """A sequence's first n_tokens slots (None: all it holds) as a uint8 blob independent of n_ctx; it does not identify the weights."""
+        n = self.sequence_position(seq) if n_tokens is None else int(n_tokens)
+        need = self.L.psh_model_seq_export(self.h, int(seq), n, None, 0)
+        if need < 0:
+            raise HostError(self.L.psh_last_error().decode())
+        blob = np.empty(need, dtype=np.uint8)
+        if self.L.psh_model_seq_export(self.h, int(seq), n, blob.ctypes.data, blob.nbytes) != need:
+            raise HostError(self.L.psh_last_error().decode())
+        return blob
+
+    def import_sequence(self, seq: int, blob):
+        b = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        if self.L.psh_model_seq_import(self.h, int(seq), b.ctypes.data, b.nbytes):
+            raise HostError(self.L.psh_last_error().decode())
 
     # ---- boundary members no model graph uses (src/graph/graph.cpp:118, ggml.hpp:227,233, core/kv_cache.hpp:120-162)
     def graph_softmax(self, x):
@@ -582,3 +618,18 @@ def softmax_long_sum(e: np.ndarray, lanes: int = 1024, shift: int = 0):
     a, b = C.c_float(), C.c_float()
     ok = lib().psh_debug_softmax_long_sum(e.ctypes.data, e.size, int(lanes), int(shift), C.byref(a), C.byref(b))
     return bool(ok), np.float32(a.value), np.float32(b.value)
+
+
+def kv_state_header(n_layers: int, kv_dim: int, head_size: int, n_tokens: int, contract: int = 0) -> np.ndarray:
+    """the 64-byte header of a saved KV state as the library writes it (csrc/ps_kv_state.h)"""
+    out = np.zeros(64, dtype=np.uint8)
+    lib().psh_debug_kv_state_header(out.ctypes.data, n_layers, kv_dim, head_size, n_tokens, contract)
+    return out
+
+
+def kv_state_check(blob, n_layers: int, kv_dim: int, head_size: int, n_ctx: int, contract: int = 0, nbytes: int | None = None):
+    """CPU build of the import check (csrc/ps_kv_state.h): (rc, n_tokens | None, reason); only the header is read, `nbytes` stands for the blob's length"""
+    b = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    n = C.c_uint64(0)
+    rc = lib().psh_debug_kv_state_check(b.ctypes.data if b.size else None, b.size if nbytes is None else int(nbytes), n_layers, kv_dim, head_size, n_ctx, contract, C.byref(n))
+    return rc, (int(n.value) if rc == 0 else None), ("" if rc == 0 else lib().psh_last_error().decode())
