@@ -19,7 +19,9 @@
 #include "ps_expf.h"
 #include "ps_ops.h"
 #include "ps_quant_dev.h"
+#include "ps_attn_dev.h"
 #include "ps_attn1_dev.h"
+#include <type_traits>
 
 namespace {
 
@@ -27,13 +29,61 @@ namespace {
 __device__ __forceinline__ float coh_load_f(const float *p) { return __uint_as_float(__hip_atomic_load((const uint32_t *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
 __device__ __forceinline__ void coh_store_f(float *p, float v) { __hip_atomic_store((uint32_t *)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// (pos0, bs) of the forward: from the launch arguments when the host knew them at enqueue time (eager batches), else from the device-resident state
-__device__ __forceinline__ int att_pos0(const psl_attn_args &a) { return a.bs_host > 0 ? a.n_kv_host - a.bs_host : a.state->pos0; }
-__device__ __forceinline__ int att_bs(const psl_attn_args &a) { return a.bs_host > 0 ? a.bs_host : a.state->bs; }
+// (round 6) KVS = psl_attn_args::kv_stream: the cached K rows and V channels of a single-token step are read ONCE per token; when the model's whole cache is larger than the
+// memory-side cache nothing of it survives to the next token, and read with plain loads it displaces everything else there and in the L2s: non-temporal loads then
+// (8B at n_kv 2048, 537 MB of cache: +2.1 % decode in the fused launch, +0.8 % here; profiles/r06_kv_nt_ab.txt, r06_nt_more_ab.txt).  A small cache (Llama-3.2-1B at 640
+// positions: 42 MB) IS served from there token after token: plain loads (1548 against 1517 tok/s with the hint, profiles/r06_ad2_nt_small_models.txt).
+template <int KVS>
+__device__ __forceinline__ float4 ad2_ld4(const float *p) {
+    if (!KVS) return *(const float4 *)p;
+    const ps_u32x4 t = __builtin_nontemporal_load((const ps_u32x4 *)p);
+    float4 r;
+    __builtin_memcpy(&r, &t, 16);
+    return r;
+}
+template <int KVS>
+__device__ __forceinline__ float seqs_ld(const float *p) {
+    if (!KVS) return *p;
+    return __builtin_nontemporal_load(p);
+}
+
+// the workgroup's slot of the timeline buffer (tools/gpu_attn_timeline.py): thread 0 of the first 1024 workgroups of column 0; null outside the timeline build
+__device__ __forceinline__ unsigned long long *att_timeline_slot(const psl_attn_args &a) {
+    int wg = blockIdx.y * gridDim.x + blockIdx.x;
+    if (PS_TIMELINE) asm volatile("" : "+v"(wg)); // (opaque)
+    return (PS_TL(a.dbg) && wg < 1024 && threadIdx.x == 0 && blockIdx.z == 0) ? a.dbg + (size_t)wg * 64 : nullptr;
+}
 
 // ---------------------------------------------------------------- rope + KV append
+// One rotated pair (pi) of head h of column i, whose cache slot is p: q in place, k into row p of the K cache (and of its fp16 mirror when there is one)
+__device__ __forceinline__ void rope_append_pair(const psl_attn_args &a, const bool isq, const int i, const int h, const int pi, const int p) {
+    const int hs = a.head_size, dim = a.n_heads * hs, kvd = a.n_kv_heads * hs, half = a.n_dims / 2, i0 = 2 * pi;
+    const int rp = a.rope_pos ? a.rope_pos[i] : p;      // RoPE position
+    const float *src = isq ? a.q + (int64_t)i * dim + h * hs : a.k + (int64_t)i * kvd + h * hs;
+    float *dst = isq ? a.q + (int64_t)i * dim + h * hs : a.k_cache + (int64_t)p * kvd + h * hs;
+    if (i0 >= a.n_dims) { // past the rotated dimensions: copied
+        dst[i0] = src[i0]; dst[i0 + 1] = src[i0 + 1];
+        if (!isq && a.k16) { a.k16[(int64_t)p * kvd + h * hs + i0] = (_Float16)src[i0]; a.k16[(int64_t)p * kvd + h * hs + i0 + 1] = (_Float16)src[i0 + 1]; }
+    } else {
+        const float c = a.rope_table[(int64_t)rp * hs + i0], s = a.rope_table[(int64_t)rp * hs + i0 + 1];
+        const int ia = a.neox ? pi : i0, ib = a.neox ? pi + half : i0 + 1;
+        const float x0 = src[ia], x1 = src[ib];
+        float ra, rb;
+        ps_rope_pair(x0, x1, c, s, ra, rb);
+        dst[ia] = ra;
+        dst[ib] = rb;
+        if (!isq && a.k16) { a.k16[(int64_t)p * kvd + h * hs + ia] = (_Float16)ra; a.k16[(int64_t)p * kvd + h * hs + ib] = (_Float16)rb; }
+    }
+}
+// Channel d of column i's v into column p of the transposed V cache (and row p of its fp16 mirror)
+__device__ __forceinline__ void v_append_elem(const psl_attn_args &a, const int i, const int d, const int p) {
+    const int kvd = a.n_kv_heads * a.head_size;
+    a.v_cache[(int64_t)d * a.n_ctx + p] = a.v[(int64_t)i * kvd + d];
+    if (a.v16) a.v16[(int64_t)p * kvd + d] = (_Float16)a.v[(int64_t)i * kvd + d];
+}
+
 __global__ void rope_append_kernel(psl_attn_args a, int bs) {
-    const int hs = a.head_size, dim = a.n_heads * hs, kvd = a.n_kv_heads * hs, half = a.n_dims / 2;
+    const int hs = a.head_size, kvd = a.n_kv_heads * hs;
     const int pos0 = att_pos0(a);
     const int64_t nq = (int64_t)bs * a.n_heads * (hs / 2), nk = (int64_t)bs * a.n_kv_heads * (hs / 2), nv = (int64_t)bs * kvd;
     for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < nq + nk + nv; o += (int64_t)gridDim.x * blockDim.x) {
@@ -43,45 +93,27 @@ __global__ void rope_append_kernel(psl_attn_args a, int bs) {
             const int nh = isq ? a.n_heads : a.n_kv_heads;
             const int pi = (int)(oo % (hs / 2));
             const int h = (int)((oo / (hs / 2)) % nh), i = (int)(oo / ((int64_t)(hs / 2) * nh));
-            const int p = pos0 + i, i0 = 2 * pi;                 // p: cache slot
-            const int rp = a.rope_pos ? a.rope_pos[i] : p;      // RoPE position
-            const float *src = isq ? a.q + (int64_t)i * dim + h * hs : a.k + (int64_t)i * kvd + h * hs;
-            float *dst = isq ? a.q + (int64_t)i * dim + h * hs : a.k_cache + (int64_t)p * kvd + h * hs;
-            if (i0 >= a.n_dims) {
-                dst[i0] = src[i0]; dst[i0 + 1] = src[i0 + 1];
-                if (!isq && a.k16) { a.k16[(int64_t)p * kvd + h * hs + i0] = (_Float16)src[i0]; a.k16[(int64_t)p * kvd + h * hs + i0 + 1] = (_Float16)src[i0 + 1]; }
-                continue;
-            }
-            const float c = a.rope_table[(int64_t)rp * hs + i0], s = a.rope_table[(int64_t)rp * hs + i0 + 1];
-            const int ia = a.neox ? pi : i0, ib = a.neox ? pi + half : i0 + 1;
-            const float x0 = src[ia], x1 = src[ib];
-            float ra, rb;
-            ps_rope_pair(x0, x1, c, s, ra, rb);
-            dst[ia] = ra;
-            dst[ib] = rb;
-            if (!isq && a.k16) { a.k16[(int64_t)p * kvd + h * hs + ia] = (_Float16)ra; a.k16[(int64_t)p * kvd + h * hs + ib] = (_Float16)rb; }
+            rope_append_pair(a, isq, i, h, pi, pos0 + i);
         } else {
             const int64_t oo = o - nq - nk;
             const int d = (int)(oo % kvd), i = (int)(oo / kvd);
-            a.v_cache[(int64_t)d * a.n_ctx + pos0 + i] = a.v[(int64_t)i * kvd + d];
-            if (a.v16) a.v16[(int64_t)(pos0 + i) * kvd + d] = (_Float16)a.v[(int64_t)i * kvd + d];
+            v_append_elem(a, i, d, pos0 + i);
         }
     }
 }
 
 // ---------------------------------------------------------------- scores: s[i][h][j] = K[j][kvh] · q[i][h]
 // grid (n_ctx/32, n_kv_heads, bs); a half-wave (32 lanes) per position, 8 half-waves x 4 rounds = 32 positions.
-constexpr int R2MAX = 8;
-template <int NV> // head_size / 32
-__global__ __launch_bounds__(256) void attn_scores_kernel(psl_attn_args a) {
+// scores_col: the 32 positions from 32 blockIdx.x on of column blockIdx.z, on the K cache of `a` -- the body of attn_scores_kernel (one cache, the forward's columns)
+// and of attn_seqs_scores_kernel (batched decode: a cache per column, seqs_col_args).  KVS: the K rows by non-temporal loads.  dbg: timeline slot or null.
+template <int NV, int KVS> // NV = head_size / 32
+__device__ __forceinline__ void scores_col(const psl_attn_args &a, unsigned long long *const dbg) {
     const int hs = NV * 32, dim = a.n_heads * hs, kvd = a.n_kv_heads * hs, r2 = a.n_heads / a.n_kv_heads;
     const int c = threadIdx.x & 31, hw = threadIdx.x >> 5;
     const int kvh = blockIdx.y, i = blockIdx.z;
     const int n_kv = att_pos0(a) + att_bs(a);
     const int j0 = blockIdx.x * 32;
     if (j0 >= n_kv) return;
-    const int wg = blockIdx.y * gridDim.x + blockIdx.x; // timeline (tools/gpu_attn_timeline.py, key 40)
-    unsigned long long *const dbg = (PS_TL(a.dbg) && wg < 1024 && threadIdx.x == 0 && blockIdx.z == 0) ? a.dbg + (size_t)wg * 64 : nullptr;
     if (dbg) { dbg[0] = __builtin_amdgcn_s_memtime(); dbg[29] = __builtin_amdgcn_s_memrealtime(); }
     const float *qb = a.q + (int64_t)i * dim + (int64_t)kvh * r2 * hs;
     float *sb       = a.scores + ((int64_t)i * a.n_heads + (int64_t)kvh * r2) * a.n_ctx;
@@ -96,7 +128,7 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(psl_attn_args a) {
         const int j     = j0 + rd * 8 + hw;
         const float *kr = a.k_cache + (int64_t)(j < n_kv ? j : 0) * kvd + kvh * hs;
 #pragma unroll
-        for (int m = 0; m < NV; m++) kf[rd][m] = kr[m * 32 + c];
+        for (int m = 0; m < NV; m++) kf[rd][m] = seqs_ld<KVS>(&kr[m * 32 + c]);
     }
     if (dbg) dbg[1] = __builtin_amdgcn_s_memtime(); // loads issued
 #pragma unroll
@@ -117,6 +149,8 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(psl_attn_args a) {
     }
     if (dbg) { dbg[3] = __builtin_amdgcn_s_memtime(); dbg[30] = __builtin_amdgcn_s_memrealtime(); }
 }
+template <int NV>
+__global__ __launch_bounds__(256) void attn_scores_kernel(psl_attn_args a) { scores_col<NV, 0>(a, att_timeline_slot(a)); } // (timeline key 40)
 
 // Batches: the same scores on the matrix cores, still bit-exact.  v_mfma_f32_16x16x4_f32 is a k-ordered f32 fma chain
 // (D = fma(a_k3, b_k3, fma(a_k2, b_k2, fma(a_k1, b_k1, fma(a_k0, b_k0, C)))), one rounding per product), and chain c of
@@ -287,12 +321,11 @@ __device__ __forceinline__ void attn_softmax_rows(const psl_attn_args &a, const 
         for (int t = 0; t < EPT; t++) {
             const int j = j0 + PV_NT * t;
             if (j < n_kv) {
-                const bool ok = (j < pos0) ? (a.kv_vis ? a.kv_vis[j] != 0 : true) : (a.tree ? a.tree[i * bs + (j - pos0)] != 0 : (j - pos0) <= i);
+                const bool ok = att_visible(a, i, bs, pos0, j);
 #pragma unroll
                 for (int g = 0; g < R2MAX; g++) {
                     if (g < r2) {
-                        float v = __fmul_rn(sv[g][t], a.scale);
-                        v       = __fadd_rn(v, ok ? 0.f : -INFINITY);
+                        const float v = att_logit(sv[g][t], a.scale, ok);
                         pl[(size_t)g * n_kv4 + j] = v;
                         rmax[g] = fmaxf(rmax[g], v);
                     }
@@ -327,8 +360,7 @@ __device__ __forceinline__ void attn_softmax_rows(const psl_attn_args &a, const 
                 for (int l = 0; l < 8; l++) v[l] = ps_v_expf(__fsub_rn(v[l], mx)); // (ps_v_expf_n here costs attn_softmax_pv_cols_kernel<2> five spilled registers)
                 *(float4 *)(pg + gi * 8)     = make_float4(v[0], v[1], v[2], v[3]);
                 *(float4 *)(pg + gi * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
-                const float a0 = __fadd_rn(v[4], v[0]), a1 = __fadd_rn(v[5], v[1]), a2 = __fadd_rn(v[6], v[2]), a3 = __fadd_rn(v[7], v[3]);
-                rs += (double)__fadd_rn(__fadd_rn(a0, a2), __fadd_rn(a1, a3));
+                rs += (double)ps_sml_group8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
             }
             if (slot == 0)
                 for (int j = n8; j < n_kv; j++) { const float e = ps_expf_glibc(__fsub_rn(pg[j], mx)); pg[j] = e; rs += (double)e; }
@@ -353,7 +385,10 @@ __device__ __forceinline__ void attn_softmax_rows(const psl_attn_args &a, const 
 //   phase 2 out[h][d] = ggml_vec_dot_f32(V[d], p[h]) (ggml.c:2126-2160): 32 fma chains over columns 32i+c, one lane
 //           each, p_j = e_j * (float)(1/sum) formed at the read (same rounding as the reference's scale pass),
 //           GGML_F32x8_REDUCE tree, n%32 leftovers (mul, add).  V comes through LDS tiles (prefetched one ahead).
-__global__ __launch_bounds__(PV_NT) void attn_softmax_pv_kernel(psl_attn_args a) {
+// softmax_pv_col: column blockIdx.z, on the caches of `a` -- the body of attn_softmax_pv_kernel (one cache) and of attn_seqs_softmax_pv_kernel (batched decode: a cache
+// per column and (pos0, bs) = (the column's position, 1), seqs_col_args).  KVS: the V rows by non-temporal loads.  dbg: timeline slot or null.
+template <int KVS>
+__device__ __forceinline__ void softmax_pv_col(const psl_attn_args &a, unsigned long long *const dbg) {
     extern __shared__ __attribute__((aligned(16))) float pl[]; // [r2][n_ctx4] e_j, then [4][PV_VSTR] V tile
     const int hs = a.head_size, dim = a.n_heads * hs, r2 = a.n_heads / a.n_kv_heads;
     const int kvh = blockIdx.y, i = blockIdx.z, bs = att_bs(a), pos0 = att_pos0(a);
@@ -362,8 +397,6 @@ __global__ __launch_bounds__(PV_NT) void attn_softmax_pv_kernel(psl_attn_args a)
     __shared__ float redf[R2MAX][PV_NW];
     __shared__ double redd[R2MAX][PV_NW];
     __shared__ float invs[R2MAX];
-    const int wg = blockIdx.y * gridDim.x + blockIdx.x; // timeline (tools/gpu_attn_timeline.py, key 41)
-    unsigned long long *const dbg = (PS_TL(a.dbg) && wg < 1024 && threadIdx.x == 0 && blockIdx.z == 0) ? a.dbg + (size_t)wg * 64 : nullptr;
     auto mark = [&](int k) { if (dbg) dbg[k] = __builtin_amdgcn_s_memtime(); };
     if (dbg) { dbg[0] = __builtin_amdgcn_s_memtime(); dbg[29] = __builtin_amdgcn_s_memrealtime(); }
 
@@ -375,7 +408,7 @@ __global__ __launch_bounds__(PV_NT) void attn_softmax_pv_kernel(psl_attn_args a)
         for (int k = 0; k < PV_LPT; k++) {
             const int f = threadIdx.x + PV_NT * k, row = f / (PV_TILE / 4), col = (f % (PV_TILE / 4)) * 4;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < 4 && t0 + col < n_kv4) v = *(const float4 *)(vbase + (int64_t)row * a.n_ctx + t0 + col); // n_kv4 <= n_ctx4: in bounds
+            if (row < 4 && t0 + col < n_kv4) v = ad2_ld4<KVS>(vbase + (int64_t)row * a.n_ctx + t0 + col); // n_kv4 <= n_ctx (a multiple of 4): in bounds
             ld[k] = v;
         }
     };
@@ -431,6 +464,7 @@ __global__ __launch_bounds__(PV_NT) void attn_softmax_pv_kernel(psl_attn_args a)
     if (live && c == 0) a.att[(int64_t)i * dim + ((int64_t)kvh * r2 + g) * hs + blockIdx.x * 4 + dl] = out;
     if (dbg) { dbg[10] = __builtin_amdgcn_s_memtime(); dbg[30] = __builtin_amdgcn_s_memrealtime(); }
 }
+__global__ __launch_bounds__(PV_NT) void attn_softmax_pv_kernel(psl_attn_args a) { softmax_pv_col<0>(a, att_timeline_slot(a)); } // (timeline key 41)
 
 // ---------------------------------------------------------------- single token: scores + soft-max + V.p in ONE launch
 // attn_decode2_kernel: K·q, soft-max and V·p of one cached token in one launch whose critical path is
@@ -468,18 +502,6 @@ __global__ __launch_bounds__(PV_NT) void attn_softmax_pv_kernel(psl_attn_args a)
 // NT = 512 threads (the 1024 of the text above were round 3's geometry: a kernel boundary behind 512-thread workgroups costs ~1.5 us less, and since ps_v_expf_n the doubled
 // per-lane work no longer outweighs it: psl_attn_decode2 below).  LPH = NT / 4 lanes per head take groups of 8 positions: LPH x 8 x TRIPS >= n_ctx
 constexpr int D2_MAXCTX = 4096;
-// (round 6) KVS = psl_attn_args::kv_stream: the cached K rows and V channels of a single-token step are read ONCE per token; when the model's whole cache is larger than the
-// memory-side cache nothing of it survives to the next token, and read with plain loads it displaces everything else there and in the L2s: non-temporal loads then
-// (8B at n_kv 2048, 537 MB of cache: +2.1 % decode in the fused launch, +0.8 % here; profiles/r06_kv_nt_ab.txt, r06_nt_more_ab.txt).  A small cache (Llama-3.2-1B at 640
-// positions: 42 MB) IS served from there token after token: plain loads (1548 against 1517 tok/s with the hint, profiles/r06_ad2_nt_small_models.txt).
-template <int KVS>
-__device__ __forceinline__ float4 ad2_ld4(const float *p) {
-    if (!KVS) return *(const float4 *)p;
-    const ps_u32x4 t = __builtin_nontemporal_load((const ps_u32x4 *)p);
-    float4 r;
-    __builtin_memcpy(&r, &t, 16);
-    return r;
-}
 template <int NV, int NT, int KVS>
 __global__ __launch_bounds__(NT) void attn_decode2_kernel(psl_attn_args a) {
     static_assert(NT == 512, "the one geometry that production runs (the parameter stays in the list for the instance names of the profile records)");
@@ -902,9 +924,9 @@ __global__ __launch_bounds__(256) void attn_softmax_probs_wave_kernel(psl_attn_a
             for (int r = 0; r < 4; r++) {
                 const int jj = j + r;
                 bool ok = false;
-                if (jj < n_kv) ok = (jj < pos0) ? (a.kv_vis ? a.kv_vis[jj] != 0 : true) : (a.tree ? a.tree[i * bs + (jj - pos0)] != 0 : (jj - pos0) <= i);
-                float x = __fmul_rn(e[r], a.scale);
-                x = __fadd_rn(x, ok ? 0.f : -INFINITY);
+                if (jj < n_kv) ok = att_visible(a, i, bs, pos0, jj);
+                float x = __fmul_rn(e[r], a.scale); // (att_logit's two statements, kept as text: through the call the unrolled trips compile to other control flow --
+                x = __fadd_rn(x, ok ? 0.f : -INFINITY); // s_mov_b64 71 -> 135, six more scalar registers; HISTORY.md round 16)
                 e[r] = jj < n_kv ? x : -INFINITY;
                 mx = fmaxf(mx, e[r]);
             }
@@ -933,10 +955,8 @@ __global__ __launch_bounds__(256) void attn_softmax_probs_wave_kernel(psl_attn_a
     float et = 0.f;
     const int jt = n8 + lane;
     if (jt < n_kv) {
-        const bool ok = (jt < pos0) ? (a.kv_vis ? a.kv_vis[jt] != 0 : true) : (a.tree ? a.tree[i * bs + (jt - pos0)] != 0 : (jt - pos0) <= i);
-        float x = __fmul_rn(sr[jt], a.scale);
-        x = __fadd_rn(x, ok ? 0.f : -INFINITY);
-        et = ps_expf_glibc(__fsub_rn(x, mx));
+        const bool ok = att_visible(a, i, bs, pos0, jt);
+        et = ps_expf_glibc(__fsub_rn(att_logit(sr[jt], a.scale, ok), mx));
         rs += (double)et;
     }
     const double tot = wave_sum_d_dpp(rs);
@@ -1291,11 +1311,11 @@ __global__ __launch_bounds__(64) void argmax_final_kernel(const float *pv, const
 
 // ---------------------------------------------------------------- batched decode: one token per sequence, every sequence on its own cache
 // Column i of the step belongs to sequence tab->col[i].seq and sits at that sequence's position p = col[i].pos: its k / v go to slot p of THAT sequence's
-// caches (s.kv), and it attends over slots [0, p] of them.  Per column the arithmetic is the single-column form of the kernels above -- rope_append_kernel,
-// attn_scores_kernel (32 lanes = the 32 chains of ggml_vec_dot_f32, k-ordered fma, GGML_F32x8_REDUCE) and attn_softmax_pv_kernel (attn_softmax_rows: ggml's
-// max / exp / double sum; V.p along the transposed V row, 32 chains, reduce, n % 32 leftovers) -- with (pos0, bs) = (p, 1), so a column's bits do not depend
-// on who else is in the batch.  Work is divided by score position (32 per workgroup) and by output channel (4 per workgroup), never along a sum, and a
-// workgroup needs no other workgroup: ragged lengths only mean that a short sequence's workgroups past its length leave at once.
+// caches (s.kv), and it attends over slots [0, p] of them.  The three kernels below are second entries to the bodies of the single-cache kernels above --
+// rope_append_pair / v_append_elem, scores_col and softmax_pv_col -- called on seqs_col_args: the launch arguments with the column's own caches and
+// (pos0, bs) = (p, 1) patched in, so a column's bits do not depend on who else is in the batch.  Work is divided by score position (32 per workgroup) and by
+// output channel (4 per workgroup), never along a sum, and a workgroup needs no other workgroup: ragged lengths only mean that a short sequence's workgroups
+// past its length leave at once.
 __device__ __forceinline__ psl_attn_args seqs_col_args(const psl_attn_args &a0, const psl_seqs_args &s, const int i) {
     psl_attn_args a = a0;
     const ps_seq_col cl = s.tab->col[i];
@@ -1303,11 +1323,12 @@ __device__ __forceinline__ psl_attn_args seqs_col_args(const psl_attn_args &a0, 
     a.k_cache = kv[0]; a.v_cache = kv[1];
     a.n_kv_host = cl.pos + 1; a.bs_host = 1; // att_pos0 = the column's position, att_bs = 1
     a.tree = nullptr; a.kv_vis = nullptr; a.rope_pos = nullptr;
+    a.k16 = nullptr; a.v16 = nullptr; // (the fp16 mirrors belong to the one-cache mode)
     return a;
 }
 
 __global__ void rope_append_seqs_kernel(psl_attn_args a0, psl_seqs_args s, int n) {
-    const int hs = a0.head_size, dim = a0.n_heads * hs, kvd = a0.n_kv_heads * hs, half = a0.n_dims / 2;
+    const int hs = a0.head_size, kvd = a0.n_kv_heads * hs;
     const int i = blockIdx.y;
     if (i >= n) return;
     const psl_attn_args a = seqs_col_args(a0, s, i);
@@ -1317,142 +1338,24 @@ __global__ void rope_append_seqs_kernel(psl_attn_args a0, psl_seqs_args s, int n
         if (o < nq + nk) {
             const bool isq = o < nq;
             const int oo = isq ? o : o - nq;
-            const int pi = oo % (hs / 2), h = oo / (hs / 2), i0 = 2 * pi;
-            const float *src = isq ? a.q + (int64_t)i * dim + h * hs : a.k + (int64_t)i * kvd + h * hs;
-            float *dst = isq ? a.q + (int64_t)i * dim + h * hs : a.k_cache + (int64_t)p * kvd + h * hs;
-            if (i0 >= a.n_dims) { dst[i0] = src[i0]; dst[i0 + 1] = src[i0 + 1]; continue; }
-            const float c = a.rope_table[(int64_t)p * hs + i0], sn = a.rope_table[(int64_t)p * hs + i0 + 1];
-            const int ia = a.neox ? pi : i0, ib = a.neox ? pi + half : i0 + 1;
-            const float x0 = src[ia], x1 = src[ib];
-            float ra, rb;
-            ps_rope_pair(x0, x1, c, sn, ra, rb);
-            dst[ia] = ra;
-            dst[ib] = rb;
-        } else {
-            const int d = o - nq - nk;
-            a.v_cache[(int64_t)d * a.n_ctx + p] = a.v[(int64_t)i * kvd + d];
-        }
+            rope_append_pair(a, isq, i, oo / (hs / 2), oo % (hs / 2), p);
+        } else v_append_elem(a, i, o - nq - nk, p);
     }
 }
 
-template <int KVS>
-__device__ __forceinline__ float seqs_ld(const float *p) {
-    if (!KVS) return *p;
-    return __builtin_nontemporal_load(p);
-}
-
-// grid (ceil(n_kv_max / 32), n_kv_heads, n): attn_scores_kernel per column on the column's own K cache
+// grid (ceil(n_kv_max / 32), n_kv_heads, n): scores_col per column on the column's own K cache
 template <int NV, int KVS>
 __global__ __launch_bounds__(256) void attn_seqs_scores_kernel(psl_attn_args a0, psl_seqs_args s) {
     const int i = blockIdx.z;
     const int n_kv = s.tab->col[i].pos + 1;
-    const int j0 = blockIdx.x * 32;
-    if (j0 >= n_kv) return;
-    const psl_attn_args a = seqs_col_args(a0, s, i);
-    const int hs = NV * 32, dim = a.n_heads * hs, kvd = a.n_kv_heads * hs, r2 = a.n_heads / a.n_kv_heads;
-    const int c = threadIdx.x & 31, hw = threadIdx.x >> 5;
-    const int kvh = blockIdx.y;
-    const float *qb = a.q + (int64_t)i * dim + (int64_t)kvh * r2 * hs;
-    float *sb       = a.scores + ((int64_t)i * a.n_heads + (int64_t)kvh * r2) * a.n_ctx;
-    float qf[R2MAX][NV];
-#pragma unroll
-    for (int g = 0; g < R2MAX; g++)
-#pragma unroll
-        for (int m = 0; m < NV; m++) qf[g][m] = (g < r2) ? qb[g * hs + m * 32 + c] : 0.f;
-    float kf[4][NV];
-#pragma unroll
-    for (int rd = 0; rd < 4; rd++) {
-        const int j     = j0 + rd * 8 + hw;
-        const float *kr = a.k_cache + (int64_t)(j < n_kv ? j : 0) * kvd + kvh * hs;
-#pragma unroll
-        for (int m = 0; m < NV; m++) kf[rd][m] = seqs_ld<KVS>(kr + m * 32 + c);
-    }
-#pragma unroll
-    for (int rd = 0; rd < 4; rd++) {
-        const int j     = j0 + rd * 8 + hw;
-        const bool live = j < n_kv;
-#pragma unroll
-        for (int g = 0; g < R2MAX; g++) {
-            if (g < r2) {
-                float sc = 0.f;
-#pragma unroll
-                for (int m = 0; m < NV; m++) sc = __fmaf_rn(kf[rd][m], qf[g][m], sc); // sum = x*y + sum, x = K row (src0)
-                sc = reduce_f32x8x4(sc);
-                if (live && c == 0) sb[(int64_t)g * a.n_ctx + j] = sc;
-            }
-        }
-    }
+    if ((int)blockIdx.x * 32 >= n_kv) return; // (before the column's cache pointers are fetched)
+    scores_col<NV, KVS>(seqs_col_args(a0, s, i), nullptr);
 }
 
-// grid (head_size / 4, n_kv_heads, n), PV_NT threads: attn_softmax_pv_kernel per column on the column's own V cache
+// grid (head_size / 4, n_kv_heads, n), PV_NT threads: softmax_pv_col per column on the column's own caches (mask: slots below pos0 visible, slot pos0 is the column itself)
 template <int KVS>
 __global__ __launch_bounds__(PV_NT) void attn_seqs_softmax_pv_kernel(psl_attn_args a0, psl_seqs_args s) {
-    extern __shared__ __attribute__((aligned(16))) float pl[]; // [r2][n_ctx4] e_j, then [4][PV_VSTR] V tile
-    const int i = blockIdx.z, kvh = blockIdx.y;
-    const psl_attn_args a = seqs_col_args(a0, s, i);
-    const int hs = a.head_size, dim = a.n_heads * hs, r2 = a.n_heads / a.n_kv_heads;
-    const int pos0 = att_pos0(a), bs = 1;
-    const int n_kv = pos0 + bs, np = n_kv & ~31, n_kv4 = (n_kv + 3) & ~3;
-    float *vt = pl + (size_t)r2 * (((size_t)a.n_ctx + 3) & ~(size_t)3);
-    __shared__ float redf[R2MAX][PV_NW];
-    __shared__ double redd[R2MAX][PV_NW];
-    __shared__ float invs[R2MAX];
-    const float *vbase = a.v_cache + ((int64_t)kvh * hs + blockIdx.x * 4) * a.n_ctx;
-    float4 ld[PV_LPT];
-    auto load_tile = [&](int t0) { // columns [t0, t0 + PV_TILE) of the 4 channel rows (zero past n_kv)
-#pragma unroll
-        for (int k = 0; k < PV_LPT; k++) {
-            const int f = threadIdx.x + PV_NT * k, row = f / (PV_TILE / 4), col = (f % (PV_TILE / 4)) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < 4 && t0 + col < n_kv4) v = ad2_ld4<KVS>(vbase + (int64_t)row * a.n_ctx + t0 + col); // n_kv4 <= n_ctx (a multiple of 4): in bounds
-            ld[k] = v;
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int k = 0; k < PV_LPT; k++) {
-            const int f = threadIdx.x + PV_NT * k, row = f / (PV_TILE / 4), col = (f % (PV_TILE / 4)) * 4;
-            if (row < 4) *(float4 *)(vt + row * PV_VSTR + col) = ld[k];
-        }
-    };
-    load_tile(0);
-    attn_softmax_rows(a, i, kvh, r2, pos0, bs, n_kv, pl, redf, redd, invs); // (mask: slots below pos0 visible, slot pos0 is the column itself)
-    store_tile();
-    __syncthreads();
-
-    // ---- V·p.  thread: chain c = tid & 31, channel dl = (tid >> 5) & 3, head g = tid >> 7
-    const int c = threadIdx.x & 31, dl = (threadIdx.x >> 5) & 3, g = threadIdx.x >> 7;
-    const bool live = g < r2;
-    const float inv = live ? invs[g] : 0.f;
-    const float *pg = pl + (size_t)(live ? g : 0) * n_kv4;
-    const float *vr = vt + dl * PV_VSTR;
-    float acc = 0.f, out = 0.f;
-    for (int t0 = 0; t0 < n_kv; t0 += PV_TILE) {
-        const int tn = min(PV_TILE, np - t0); // chain columns of this tile (multiple of 32, may be <= 0 on a leftover-only tile)
-        if (t0 > 0) {
-            __syncthreads(); // previous tile consumed
-            store_tile();
-            __syncthreads();
-        }
-        if (t0 + PV_TILE < n_kv) load_tile(t0 + PV_TILE); // next tile streams in while this one is consumed
-        if (live) {
-            int j = c;
-            for (; j + 7 * 32 < tn; j += 8 * 32) {
-                float v[8], e[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) { v[k] = vr[j + 32 * k]; e[k] = pg[t0 + j + 32 * k]; }
-#pragma unroll
-                for (int k = 0; k < 8; k++) acc = __fmaf_rn(v[k], __fmul_rn(e[k], inv), acc); // x = V row (src0), y = p
-            }
-            for (; j < tn; j += 32) acc = __fmaf_rn(vr[j], __fmul_rn(pg[t0 + j], inv), acc);
-            if (t0 + PV_TILE >= n_kv) { // last tile: reduce the 32 chains, then the n%32 leftovers in order
-                float sres = reduce_f32x8x4(acc);
-                for (int jj = np; jj < n_kv; jj++) sres = ps_dot_left(sres, vr[jj - t0], __fmul_rn(pg[jj], inv), jj - np, n_kv - np);
-                out = sres;
-            }
-        }
-    }
-    if (live && c == 0) a.att[(int64_t)i * dim + ((int64_t)kvh * r2 + g) * hs + blockIdx.x * 4 + dl] = out;
+    softmax_pv_col<KVS>(seqs_col_args(a0, s, blockIdx.z), nullptr);
 }
 
 __global__ void seqs_advance_kernel(ps_seq_table *tab, const int32_t *argmax, int32_t *tokens, int32_t *ids, int n) {
@@ -1468,6 +1371,22 @@ __global__ void seqs_advance_kernel(ps_seq_table *tab, const int32_t *argmax, in
     if (i == 0) tab->n_out = k + 1;
 }
 
+// ---------------------------------------------------------------- launchers
+// f(std::integral_constant<int, NV>) with NV = head_size / 32 of the four head sizes the kernels are built for: 128, 64, 32, and 96 otherwise
+template <class F>
+void with_nv(const int head_size, F &&f) {
+    if (head_size == 128) f(std::integral_constant<int, 4>{});
+    else if (head_size == 64) f(std::integral_constant<int, 2>{});
+    else if (head_size == 32) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 3>{});
+}
+// f(std::integral_constant<int, KVS>): the kernels' non-temporal form (KVS = 1) when kv_stream is set
+template <class F>
+void with_kvs(const int kv_stream, F &&f) {
+    if (kv_stream) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
 } // namespace
 
 void psl_rope_append_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs_args &s, int n) {
@@ -1478,21 +1397,12 @@ void psl_rope_append_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs
 void psl_attn_seqs(hipStream_t st, const psl_attn_args &a, const psl_seqs_args &s, int n) {
     const int nk = s.n_kv_max > 0 && s.n_kv_max < a.n_ctx ? s.n_kv_max : a.n_ctx;
     const dim3 gs((unsigned)((nk + 31) / 32), (unsigned)a.n_kv_heads, (unsigned)n);
-#define PS_SEQS_SCORES(NV) do { if (s.kv_stream) hipLaunchKernelGGL((attn_seqs_scores_kernel<NV, 1>), gs, dim3(256), 0, st, a, s); \
-                                else hipLaunchKernelGGL((attn_seqs_scores_kernel<NV, 0>), gs, dim3(256), 0, st, a, s); } while (0)
-    if (a.head_size == 128) PS_SEQS_SCORES(4);
-    else if (a.head_size == 64) PS_SEQS_SCORES(2);
-    else if (a.head_size == 32) PS_SEQS_SCORES(1);
-    else PS_SEQS_SCORES(3); // head_size 96
-#undef PS_SEQS_SCORES
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) {
-        (void)hipFuncSetAttribute((const void *)attn_seqs_softmax_pv_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_seqs_softmax_pv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    }
     const dim3 gp((unsigned)(a.head_size / 4), (unsigned)a.n_kv_heads, (unsigned)n);
-    if (s.kv_stream) hipLaunchKernelGGL(attn_seqs_softmax_pv_kernel<1>, gp, dim3(PV_NT), psl_attn_softmax_pv_lds(a), st, a, s);
-    else hipLaunchKernelGGL(attn_seqs_softmax_pv_kernel<0>, gp, dim3(PV_NT), psl_attn_softmax_pv_lds(a), st, a, s);
+    ps_lds_opt_in<attn_seqs_softmax_pv_kernel<0>, attn_seqs_softmax_pv_kernel<1>>();
+    with_kvs(s.kv_stream, [&](auto kvs) {
+        with_nv(a.head_size, [&](auto nv) { hipLaunchKernelGGL((attn_seqs_scores_kernel<nv.value, kvs.value>), gs, dim3(256), 0, st, a, s); });
+        hipLaunchKernelGGL(attn_seqs_softmax_pv_kernel<kvs.value>, gp, dim3(PV_NT), psl_attn_softmax_pv_lds(a), st, a, s);
+    });
 }
 
 void psl_seqs_advance(hipStream_t st, ps_seq_table *tab, const int32_t *argmax, int32_t *tokens, int32_t *ids, int n) {
@@ -1512,17 +1422,11 @@ void psl_attn_scores(hipStream_t st, const psl_attn_args &a, int bs) {
     const int nk = a.n_kv_host > 0 && a.n_kv_host < a.n_ctx ? a.n_kv_host : a.n_ctx;
     if (bs >= 8) { // batches: matrix cores (exact f32 chains), one wave per 16 positions
         dim3 gm((unsigned)((nk + 63) / 64), (unsigned)a.n_kv_heads, (unsigned)SCM_Z);
-        if (a.head_size == 128) hipLaunchKernelGGL(attn_scores_mfma_kernel<4>, gm, dim3(256), 0, st, a);
-        else if (a.head_size == 64) hipLaunchKernelGGL(attn_scores_mfma_kernel<2>, gm, dim3(256), 0, st, a);
-        else if (a.head_size == 32) hipLaunchKernelGGL(attn_scores_mfma_kernel<1>, gm, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(attn_scores_mfma_kernel<3>, gm, dim3(256), 0, st, a);
+        with_nv(a.head_size, [&](auto nv) { hipLaunchKernelGGL(attn_scores_mfma_kernel<nv.value>, gm, dim3(256), 0, st, a); });
         return;
     }
     dim3 g((unsigned)((nk + 31) / 32), (unsigned)a.n_kv_heads, (unsigned)bs);
-    if (a.head_size == 128) hipLaunchKernelGGL(attn_scores_kernel<4>, g, dim3(256), 0, st, a);
-    else if (a.head_size == 64) hipLaunchKernelGGL(attn_scores_kernel<2>, g, dim3(256), 0, st, a);
-    else if (a.head_size == 32) hipLaunchKernelGGL(attn_scores_kernel<1>, g, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(attn_scores_kernel<3>, g, dim3(256), 0, st, a); // head_size 96
+    with_nv(a.head_size, [&](auto nv) { hipLaunchKernelGGL(attn_scores_kernel<nv.value>, g, dim3(256), 0, st, a); });
 }
 
 size_t psl_attn_softmax_pv_lds(const psl_attn_args &a) {
@@ -1537,11 +1441,7 @@ void psl_attn_pv_mfma(hipStream_t st, const psl_attn_args &a, int bs) {
     const int r2p = a.n_heads / a.n_kv_heads;
     const dim3 gpv((unsigned)((bs * r2p + 15) / 16), (unsigned)a.n_kv_heads);
     if (a.head_size == 128 || a.head_size == 64) {
-        static unsigned long long attrl = 0;
-        if (ps_first_on_device(&attrl)) {
-            (void)hipFuncSetAttribute((const void *)attn_pv_mfma_lds_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-            (void)hipFuncSetAttribute((const void *)attn_pv_mfma_lds_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        }
+        ps_lds_opt_in<attn_pv_mfma_lds_kernel<8>, attn_pv_mfma_lds_kernel<4>>();
         if (a.head_size == 128) hipLaunchKernelGGL(attn_pv_mfma_lds_kernel<8>, gpv, dim3(512), 2 * 9 * 16 * PVM_RS * 4, st, a);
         else hipLaunchKernelGGL(attn_pv_mfma_lds_kernel<4>, gpv, dim3(256), 2 * 5 * 16 * PVM_RS * 4, st, a);
         return;
@@ -1550,8 +1450,7 @@ void psl_attn_pv_mfma(hipStream_t st, const psl_attn_args &a, int bs) {
 }
 void psl_attn_softmax_pv(hipStream_t st, const psl_attn_args &a, int bs) {
     if (bs >= 8 && a.head_size % 16 == 0) { // prefill chunks / wide trees: soft-max in place, then V·p on the matrix cores
-        static unsigned long long attrp = 0; // devices that have the attribute
-        if (ps_first_on_device(&attrp)) { (void)hipFuncSetAttribute((const void *)attn_softmax_probs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); }
+        ps_lds_opt_in<attn_softmax_probs_kernel>();
         const int r2p = a.n_heads / a.n_kv_heads;
         const size_t ldsp = (size_t)r2p * (((size_t)a.n_ctx + 3) & ~(size_t)3) * 4;
         if (a.n_ctx <= 64 * 4 * SMW_MAXQ) hipLaunchKernelGGL(attn_softmax_probs_wave_kernel, dim3((unsigned)((bs * a.n_heads + 3) / 4)), dim3(256), 0, st, a);
@@ -1562,11 +1461,7 @@ void psl_attn_softmax_pv(hipStream_t st, const psl_attn_args &a, int bs) {
     if (bs > 1) { // batches: one workgroup per (kv head, column pair)
         const int r2 = a.n_heads / a.n_kv_heads;
         const size_t row = ((size_t)a.n_ctx + 3) & ~(size_t)3, lds2 = 2 * r2 * row * 4, lds1 = r2 * row * 4;
-        static unsigned long long attr2 = 0; // devices that have the attribute
-        if (ps_first_on_device(&attr2)) {
-            (void)hipFuncSetAttribute((const void *)attn_softmax_pv_cols_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-            (void)hipFuncSetAttribute((const void *)attn_softmax_pv_cols_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        }
+        ps_lds_opt_in<attn_softmax_pv_cols_kernel<2>, attn_softmax_pv_cols_kernel<1>>();
         // few (kv head, column pair) workgroups (tree verify, prefill tails): split the head channels over blockIdx.z
         const bool two = lds2 <= 150 * 1024;
         const int wgs = a.n_kv_heads * (two ? (bs + 1) / 2 : bs);
@@ -1576,8 +1471,7 @@ void psl_attn_softmax_pv(hipStream_t st, const psl_attn_args &a, int bs) {
         else hipLaunchKernelGGL(attn_softmax_pv_cols_kernel<1>, dim3((unsigned)a.n_kv_heads, (unsigned)bs, nz), dim3(PV_NT), lds1, st, a);
         return;
     }
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) { (void)hipFuncSetAttribute((const void *)attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); }
+    ps_lds_opt_in<attn_softmax_pv_kernel>();
     dim3 g((unsigned)(a.head_size / 4), (unsigned)a.n_kv_heads, (unsigned)bs);
     psk_note_attn("attn_scores_kernel<%d> + attn_softmax_pv_kernel", a.head_size / 32); // (bs == 1: psl_attn_scores took attn_scores_kernel)
     hipLaunchKernelGGL(attn_softmax_pv_kernel, g, dim3(PV_NT), psl_attn_softmax_pv_lds(a), st, a);
@@ -1607,15 +1501,11 @@ bool psl_attn_decode2(hipStream_t st, int n_cu, const psl_attn_args &a) {
     // slower in total (14.05 vs 13.66 us: twice the soft-max numerators per lane, issue-bound); with ps_v_expf_n they win: 8B decode 534.9 -> 542.8 tok/s
     // (profiles/r04_gemv_variants.txt); the 1024-thread instances left with round 12.
     psk_note_attn("attn_decode2_kernel<%d, %d, %d>", a.head_size / 32, 512, a.kv_stream ? 1 : 0);
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) {
-        (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<4, 512, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<4, 512, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<2, 512, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_decode2_kernel<2, 512, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    }
-    if (a.head_size == 128) { if (a.kv_stream) hipLaunchKernelGGL((attn_decode2_kernel<4, 512, 1>), g, dim3(512), lds, st, a); else hipLaunchKernelGGL((attn_decode2_kernel<4, 512, 0>), g, dim3(512), lds, st, a); }
-    else { if (a.kv_stream) hipLaunchKernelGGL((attn_decode2_kernel<2, 512, 1>), g, dim3(512), lds, st, a); else hipLaunchKernelGGL((attn_decode2_kernel<2, 512, 0>), g, dim3(512), lds, st, a); }
+    ps_lds_opt_in<attn_decode2_kernel<4, 512, 0>, attn_decode2_kernel<4, 512, 1>, attn_decode2_kernel<2, 512, 0>, attn_decode2_kernel<2, 512, 1>>();
+    with_kvs(a.kv_stream, [&](auto kvs) { // (head sizes 128 and 64 only: no other instance exists)
+        if (a.head_size == 128) hipLaunchKernelGGL((attn_decode2_kernel<4, 512, kvs.value>), g, dim3(512), lds, st, a);
+        else hipLaunchKernelGGL((attn_decode2_kernel<2, 512, kvs.value>), g, dim3(512), lds, st, a);
+    });
     return true;
 }
 

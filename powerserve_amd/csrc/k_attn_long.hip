@@ -11,17 +11,13 @@
 #include "ps_dev.h"
 #include "ps_expf.h"
 #include "ps_ops.h"
-#include "ps_softmax_long_dev.h"
+#include "ps_attn_dev.h"
 
 static_assert(PS_SML_N_MAX == PS_HIP_LONG_CTX_MAX + 64, "ps_softmax_long_dev.h and include/ps_hip.h disagree");
 
 namespace {
 
-__device__ __forceinline__ int att_pos0(const psl_attn_args &a) { return a.bs_host > 0 ? a.n_kv_host - a.bs_host : a.state->pos0; }
-__device__ __forceinline__ int att_bs(const psl_attn_args &a) { return a.bs_host > 0 ? a.bs_host : a.state->bs; }
-
 constexpr int SML_NT = 1024, SML_NW = SML_NT / 64;
-constexpr int R2MAX = 8;
 
 // rows soft-maxed by the long kernels, of them through the sequential sum.  A device global: one per device and per loaded library (a process that loads the
 // default AND the -DPS_CONTRACT library has two sets, each counting its own launches); ps_hip_softmax_long_counters adds up the devices this library launched on
@@ -119,11 +115,7 @@ __global__ __launch_bounds__(SML_NT) void attn_softmax_long_kernel(psl_attn_args
     extern __shared__ __attribute__((aligned(16))) float gsl[];
     const int h = blockIdx.x, i = blockIdx.y, bs = att_bs(a), pos0 = att_pos0(a), n_kv = pos0 + bs;
     float *row = a.scores + ((int64_t)i * a.n_heads + h) * a.n_ctx;
-    // scale + mask exactly as attn_softmax_rows: fmul(scale), fadd(0 / -inf); visibility from kv_vis (cached slots), tree or causality (this forward's columns)
-    auto logit = [&](const float s, const int j) {
-        const bool ok = (j < pos0) ? (a.kv_vis ? a.kv_vis[j] != 0 : true) : (a.tree ? a.tree[i * bs + (j - pos0)] != 0 : (j - pos0) <= i);
-        return __fadd_rn(__fmul_rn(s, a.scale), ok ? 0.f : -INFINITY);
-    };
+    auto logit = [&](const float s, const int j) { return att_logit(s, a.scale, att_visible(a, i, bs, pos0, j)); }; // (as attn_softmax_rows)
     sml_row<true>(n_kv, row, shift, gsl,
                   [&](int gi, float (&v)[8]) {
                       const float4 lo = *(const float4 *)(row + (size_t)gi * 8), hi = *(const float4 *)(row + (size_t)gi * 8 + 4);
@@ -254,15 +246,10 @@ int psl_attn_long_set_tile(int positions) {
 static size_t sml_lds(int n) { return ((size_t)n / 8 + 8) * 4; }
 static unsigned long long g_sml_devs = 0; // devices the long kernels have been launched on: whose counters exist
 static void sml_attrs() {
-    static unsigned long long attr = 0; // devices that have the attributes
-    if (ps_first_on_device(&attr)) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev < 64) g_sml_devs |= 1ull << dev;
-        (void)hipFuncSetAttribute((const void *)attn_softmax_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sml_lds(PS_SML_N_MAX));
-        (void)hipFuncSetAttribute((const void *)softmax_long_ext_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sml_lds(PS_SML_N_MAX));
-        (void)hipFuncSetAttribute((const void *)attn_pv_long_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_pv_long_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    }
+    if (!ps_lds_opt_in<attn_softmax_long_kernel, softmax_long_ext_kernel>((int)sml_lds(PS_SML_N_MAX))) return;
+    ps_lds_opt_in<attn_pv_long_kernel<0>, attn_pv_long_kernel<1>>(); // (the first launch on this device)
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && dev < 64) g_sml_devs |= 1ull << dev;
 }
 
 // soft-max + V.p of a long-window model behind psl_attn_scores(st, a, bs)

@@ -5,6 +5,7 @@
 #pragma once
 #include "ps_dev.h"
 #include "ps_expf.h"
+#include "ps_softmax_long_dev.h"
 
 namespace {
 typedef float ps_f32x4 __attribute__((ext_vector_type(4)));
@@ -51,8 +52,7 @@ __device__ __forceinline__ float a1_score(const float4 (&kf)[NV], const float *q
 // e_j = exp(x_j - max) of a whole group of 8 (ggml_v_expf) in place, and the group's sum by the reference's in-group tree (ggml.c:2831-2866)
 __device__ __forceinline__ float a1_exp8(float (&sv)[8], const float mx) {
     ps_v_expf_n<8>(sv, mx);
-    const float a0 = __fadd_rn(sv[4], sv[0]), a1 = __fadd_rn(sv[5], sv[1]), a2 = __fadd_rn(sv[6], sv[2]), a3 = __fadd_rn(sv[7], sv[3]);
-    return __fadd_rn(__fadd_rn(a0, a2), __fadd_rn(a1, a3));
+    return ps_sml_group8(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7]);
 }
 
 // one step of V.p on v_mfma_f32_16x16x4_f32, a k-ordered fma chain with one rounding per product: p_j = e_j * (float)(1/sum) formed where it is used (the same single

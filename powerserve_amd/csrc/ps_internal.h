@@ -85,6 +85,17 @@ static inline bool ps_first_on_device(unsigned long long *mask) {
     return true;
 }
 
+// Opt KERNELS in to `bytes` of dynamic LDS (above the 64 KiB a kernel gets unasked), once per device; one call site per set of kernels.  True: this was the
+// first call on the current device.
+constexpr int PS_LDS_MAX = 156 * 1024; // what the large attention kernels ask for
+template <auto... KERNELS>
+static inline bool ps_lds_opt_in(const int bytes = PS_LDS_MAX) {
+    static unsigned long long done = 0; // devices that have the attribute
+    if (!ps_first_on_device(&done)) return false;
+    ((void)hipFuncSetAttribute((const void *)KERNELS, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), ...);
+    return true;
+}
+
 #define PS_CHECK(ctx, call)                                                                          \
     do {                                                                                             \
         hipError_t e_ = (call);                                                                      \

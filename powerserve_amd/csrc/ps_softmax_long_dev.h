@@ -24,10 +24,17 @@
 #define PS_SML_N_MAX (131072 + 64) // PS_HIP_LONG_CTX_MAX + 64 elements: the longest row
 #define PS_SML_GROUPS_MAX (PS_SML_N_MAX / 8)
 
-// the reference's in-group association (ggml.c:2829-2833): (hi128 + lo128), movehl, movehdup
+// the reference's in-group association (ggml.c:2829-2833): (hi128 + lo128), movehl, movehdup.  The only copy: the single-token kernels (a1_exp8), attn_softmax_rows and
+// the long rows take it from here.  Seven additions and nothing else, each rounded on its own: on the device they are __fadd_rn, which no contraction setting of a
+// build (PS_CONTRACT) can fuse with a multiply of an inlined caller
 PS_HD float ps_sml_group8(const float v0, const float v1, const float v2, const float v3, const float v4, const float v5, const float v6, const float v7) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float a0 = __fadd_rn(v4, v0), a1 = __fadd_rn(v5, v1), a2 = __fadd_rn(v6, v2), a3 = __fadd_rn(v7, v3);
+    return __fadd_rn(__fadd_rn(a0, a2), __fadd_rn(a1, a3));
+#else
     const float a0 = v4 + v0, a1 = v5 + v1, a2 = v6 + v2, a3 = v7 + v3;
     return (a0 + a2) + (a1 + a3);
+#endif
 }
 PS_HD int ps_sml_terms(int n) { return n / 8 + n % 8; }
 PS_HD double ps_sml_eps(int n, int shift) { return ldexp((double)ps_sml_terms(n), shift - 51); }

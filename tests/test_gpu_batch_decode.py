@@ -110,6 +110,70 @@ def test_batch_equals_oracle_tiny(ctx, oracle, tmp_path, preset, wt):
         om.close()
 
 
+# the head sizes and head ratios the tiny presets do not reach -- head size 96 (three 32-lane blocks per row), head size 32 with one query head per kv head, eight
+# query heads per kv head (the most the column kernels hold) -- with both load forms of the per-sequence kernels forced (ps_hip_debug_set(9, 0 / 1): plain / non-temporal)
+ODD_PRESETS = ["odd-llama-hs96", "odd-llama-hs32", "odd-llama-r8"]
+ODD_LENS = [1, 31, 33, 70]  # prompts that end before, at and behind a 32-position block, leaving n % 8 and n % 32 tails
+ODD_STEPS = 6
+
+
+@pytest.fixture(scope="module")
+def odd_refs(tmp_path_factory):
+    """per preset, filled on first use and then only read: the model directory, the prompts, the forced tokens, and the oracle's logits and caches"""
+    return {"base": tmp_path_factory.mktemp("odd"), "refs": {}}
+
+
+def odd_reference(odd_refs, oracle, preset):
+    if preset in odd_refs["refs"]:
+        return odd_refs["refs"][preset]
+    d, mj, cfg = make(odd_refs["base"], preset, 8, 128, seed=29, name=preset)
+    tensors = load_tensors(os.path.join(d, "ggml/weights.gguf"))
+    rng = np.random.default_rng(23)
+    prompts = [rng.integers(0, cfg.vocab_size, n) for n in ODD_LENS]
+    forced = rng.integers(0, cfg.vocab_size, (ODD_STEPS, len(ODD_LENS)))
+    want, kc, vc = [], [], []
+    for s, p in enumerate(prompts):  # one independent oracle model per sequence
+        om = oracle.model(cfg, mj["model_arch"], tensors, n_threads=4)
+        oracle_prefill(om, p, 8)
+        want.append([om.forward([int(forced[k, s])], [len(p) + k], True)[0].copy() for k in range(ODD_STEPS)])
+        n = len(p) + ODD_STEPS
+        kc.append([om.k_cache(L)[:n].copy() for L in range(cfg.n_layers)])
+        vc.append([om.v_cache(L)[:, :n].copy() for L in range(cfg.n_layers)])
+        om.close()
+    odd_refs["refs"][preset] = (d, cfg, prompts, forced, want, kc, vc)
+    return odd_refs["refs"][preset]
+
+
+@pytest.mark.parametrize("kvs", [0, 1])
+@pytest.mark.parametrize("preset", ODD_PRESETS)
+def test_batch_equals_oracle_odd_shapes(ctx, oracle, odd_refs, preset, kvs):
+    from powerserve_amd import hip
+    d, cfg, prompts, forced, want, kc, vc = odd_reference(odd_refs, oracle, preset)
+    assert ctx.L.ps_hip_debug_set(9, kvs) == 0
+    try:
+        gm = hip.Model(ctx, d, max_batch=16)
+        gm.seq_reserve(len(prompts))
+        for s, p in enumerate(prompts):
+            gm.seq_select(s)
+            gm.prefill(p, 8)
+            assert gm.seq_position(s) == len(p)
+        for k in range(ODD_STEPS):
+            lg, am = gm.decode_batch(np.arange(len(prompts)), forced[k])
+            for s in range(len(prompts)):
+                assert same(lg[s], want[s][k]), (k, s)
+                assert int(am[s]) == int(np.argmax(want[s][k])), (k, s)
+        for s, p in enumerate(prompts):
+            n = len(p) + ODD_STEPS
+            assert gm.seq_position(s) == n
+            gm.seq_select(s)
+            for L in range(cfg.n_layers):
+                assert same(gm.k_cache(L)[:n], kc[s][L]), (s, L)
+                assert same(gm.v_cache(L)[:, :n], vc[s][L]), (s, L)
+        gm.close()
+    finally:
+        ctx.L.ps_hip_debug_set(9, -1)
+
+
 # ---------------------------------------------------------------- 2. batch equals solo on the device, real layer shapes
 # 8B Q4_K (cut to 2 layers), Llama-3.2-1B Q4_0 (head size 64), Q4_K_M mix (all 4 layers: Q4_K V in layers 0 and 1, Q6_K V in 2 and 3); third field: layers kept (0 = all)
 SHAPES = [("llama-8b-dims-4l", 12, 2), ("llama-1b-dims-2l", 2, 0), ("llama-8b-dims-4l", 1015, 0)]
