@@ -90,6 +90,39 @@ constexpr int G4K_XCH = G4K_NST * G4K_STAGE + 32;   // after the stages and the 
 constexpr int G4K_TAB = G4K_XCH + 4 * 64 * 48 * 4;   // glibc expf's exp2 table (ps_expf.h), for the SiLU epilogue: an LDS look-up, not a global one
 constexpr int G4K_LDS = G4K_TAB + PS_EXP2F_N * 8;
 
+// ---- the statements every kernel of this file must round exactly where ggml rounds: ONE copy each.  All of them take values and return values, which compiles
+// to what the kernels had as text (tools/isa_diff.py); what derives addresses stays in the kernels.
+// hsum_float_8 (ggml-quants.c:62-68) over the eight accumulator lanes: lane u + lane u + 4 first, then (0 + 2) + (1 + 3); the four acc_m lanes as row_reduce<PS_Q4_K> does
+__device__ __forceinline__ float g4k_hsum8(const float a0, const float a1, const float a2, const float a3, const float a4, const float a5, const float a6, const float a7) {
+    const float s0 = __fadd_rn(a0, a4), s1 = __fadd_rn(a1, a5), s2 = __fadd_rn(a2, a6), s3 = __fadd_rn(a3, a7);
+    return __fadd_rn(__fadd_rn(s0, s2), __fadd_rn(s1, s3));
+}
+__device__ __forceinline__ float g4k_hsum4(const float m0, const float m1, const float m2, const float m3) { return __fadd_rn(__fadd_rn(m0, m2), __fadd_rn(m1, m3)); }
+// ps_silu_mul with glibc's exp2 table in LDS (tab)
+__device__ __forceinline__ float g4k_silu_mul(const float g, const float u, const uint64_t *tab) {
+    return __fmul_rn(__fmul_rn(g, __fdiv_rn(1.0f, __fadd_rn(1.0f, ps_expf_glibc(-g, tab)))), u);
+}
+// a Q4_K header h (16 B: d | dmin, then the twelve scale bytes, get_scale_min_k4): the 6-bit scales / mins of sub-blocks 0..3 (hi = 0) or 4..7, one per byte
+template <class H> __device__ __forceinline__ uint32_t g4k_scale_bytes(const H h, const int hi) { return hi ? ((h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4)) : (h.y & 0x3f3f3f3fu); }
+template <class H> __device__ __forceinline__ uint32_t g4k_min_bytes(const H h, const int hi) { return hi ? (((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4)) : (h.z & 0x3f3f3f3fu); }
+// byte sel & 3 of b (a scale or a min, < 64), twice, as an fp16 pair: bytes (x, 0x64, x, 0x64) are (1024 + x, 1024 + x), and minus 1024 is exact
+__device__ __forceinline__ g4k_h2 g4k_byte_h2(const uint32_t b, const uint32_t sel) {
+    const g4k_h2 k1024 = {(_Float16)1024.f, (_Float16)1024.f};
+    const uint32_t t = __builtin_amdgcn_perm(0x64646464u, b, sel);
+    g4k_h2 v;
+    __builtin_memcpy(&v, &t, 4);
+    return v - k1024;
+}
+// two dwords as the four fp16 of a K = 16 operand (the mins products)
+__device__ __forceinline__ g4k_h4 g4k_h4_of(const uint32_t x, const uint32_t y) {
+    g4k_h2 a, b;
+    __builtin_memcpy(&a, &x, 4); __builtin_memcpy(&b, &y, 4);
+    return g4k_h4{a[0], a[1], b[0], b[1]};
+}
+// hx = the header's first dword (fp16 d, dmin), yd the column's scale: d * yd and -dmin * yd as the reference forms them
+__device__ __forceinline__ float g4k_yd_d(const uint32_t hx, const float yd) { return __fmul_rn(yd, ps_h2f((uint16_t)(hx & 0xffff))); }
+__device__ __forceinline__ float g4k_yd_dmin(const uint32_t hx, const float yd) { return __fmul_rn(-yd, ps_h2f((uint16_t)(hx >> 16))); }
+
 // the two row tiles of a task
 struct G4KRows { const uint8_t *qs[2], *aux[2], *qh[2]; int tile[2]; };
 
@@ -102,15 +135,12 @@ template <int UPP, int WT> // accumulator lanes per producer wave: u = UPP hw ..
 __device__ __forceinline__ void g4k_produce(const uint2 (&qq)[UPP], const uint32_t (&hq)[UPP], const uint4 h, char *st, const int row, const int hw, const int p) {
     // the four sub-block scales 4p .. 4p+3 (get_scale_min_k4: 0..3 sit in the low 6 bits of scale bytes 0..3, 4..7 are
     // spread over bytes 8..11 and the top bits of bytes 0..3) as fp16 pairs (s, s) and (-1024 s, -1024 s)
-    const uint32_t scb = p ? ((h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4)) : (h.y & 0x3f3f3f3fu);
-    const g4k_h2 k1024 = {(_Float16)1024.f, (_Float16)1024.f}, km1024 = {(_Float16)-1024.f, (_Float16)-1024.f};
+    const uint32_t scb = g4k_scale_bytes(h, p);
+    const g4k_h2 km1024 = {(_Float16)-1024.f, (_Float16)-1024.f};
     g4k_h2 sc[4], nc[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) { // bytes (s, 0x64, s, 0x64) = the fp16 pair (1024 + s, 1024 + s); minus 1024 is exact
-        const uint32_t t = __builtin_amdgcn_perm(0x64646464u, scb, 0x04000400u | (uint32_t)(i * 0x00010001u));
-        g4k_h2 v;
-        __builtin_memcpy(&v, &t, 4);
-        sc[i] = v - k1024;
+    for (int i = 0; i < 4; i++) {
+        sc[i] = g4k_byte_h2(scb, 0x04000400u | (uint32_t)(i * 0x00010001u));
         nc[i] = sc[i] * km1024; // (<= 64512: exact)
     }
 #pragma unroll
@@ -139,19 +169,13 @@ __device__ __forceinline__ void g4k_produce(const uint2 (&qq)[UPP], const uint32
         }
     }
     if (hw == 0 && p == 0) { // once per row: the mins operands
-        const uint32_t mn03 = h.z & 0x3f3f3f3fu;
-        const uint32_t mn47 = ((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4);
+        const uint32_t mn03 = g4k_min_bytes(h, 0), mn47 = g4k_min_bytes(h, 1);
         uint32_t o[8];
 #pragma unroll
         for (int v = 0; v < 4; v++) {
             const uint32_t mp = (v < 2) ? mn03 : mn47;
             const int e = (2 * v) & 3;
-            // bytes (m, 0x64, m, 0x64) = the fp16 pair (1024 + m, 1024 + m); minus 1024 is exact
-            const uint32_t p0 = __builtin_amdgcn_perm(0x64646464u, mp, 0x04000400u | (uint32_t)(e * 0x00010001u));
-            const uint32_t p1 = __builtin_amdgcn_perm(0x64646464u, mp, 0x04000400u | (uint32_t)((e + 1) * 0x00010001u));
-            g4k_h2 h0, h1;
-            __builtin_memcpy(&h0, &p0, 4); __builtin_memcpy(&h1, &p1, 4);
-            h0 = h0 - k1024; h1 = h1 - k1024;
+            const g4k_h2 h0 = g4k_byte_h2(mp, 0x04000400u | (uint32_t)(e * 0x00010001u)), h1 = g4k_byte_h2(mp, 0x04000400u | (uint32_t)((e + 1) * 0x00010001u));
             __builtin_memcpy(&o[2 * v], &h0, 4); __builtin_memcpy(&o[2 * v + 1], &h1, 4);
         }
         *(uint4 *)(st + G4K_MINS + row * 32) = make_uint4(o[0], o[1], o[2], o[3]);
@@ -196,6 +220,10 @@ __device__ __forceinline__ void g4k_store_pair(const G4KParams &p, const int wi,
 // of its 32).  The n_cb / cbx groups of cbx column blocks are dealt over the XCDs; the 8 cbx / n_cb XCDs that share a group split the tasks
 // between them.  An XCD then cycles only cbx x 0.55 MB of activations and streams 1 / (8 cbx / n_cb) of the weights, each weight tile met by
 // cbx workgroups of that XCD at the same time.
+__device__ __forceinline__ void g4k_item_rr(const int n_cb, const int i, int &task, int &cb) { // the round-2 order (the Q6_K kernel has no other)
+    cb = (i >> 3) % n_cb;
+    task = (i / (8 * n_cb)) * 8 + (i & 7);
+}
 __device__ __forceinline__ void g4k_item(const G4KParams &p, const int i, int &task, int &cb) {
     if (p.cbx) {
         const int b = i & 255, k = i >> 8, xcd = b & 7, slot = b >> 3;
@@ -204,8 +232,7 @@ __device__ __forceinline__ void g4k_item(const G4KParams &p, const int i, int &t
         task = (k * NT + slot / p.cbx) * TC + xcd / G;
         return;
     }
-    cb = (i >> 3) % p.n_cb;
-    task = (i / (8 * p.n_cb)) * 8 + (i & 7);
+    g4k_item_rr(p.n_cb, i, task, cb);
 }
 template <int EPI>
 __device__ __forceinline__ G4KRows g4k_rows(const G4KParams &p, const int task, int &wi, int &pair) {
@@ -220,13 +247,37 @@ __device__ __forceinline__ G4KRows g4k_rows(const G4KParams &p, const int task, 
     else { R.qs[0] = R.qs[1] = W.qs; R.aux[0] = R.aux[1] = W.aux; R.qh[0] = R.qh[1] = W.qh; R.tile[0] = 2 * pair; R.tile[1] = 2 * pair + 1; }
     return R;
 }
-__device__ __forceinline__ int g4k_next_item(const G4KParams &p, int i) { // the next item of this workgroup with a real task, or n_items
+template <class P> // G4KParams or G6KParams (g4k_item has an overload for each)
+__device__ __forceinline__ int g4k_next_item(const P &p, int i) { // the next item of this workgroup with a real task, or n_items
     for (i += (int)gridDim.x; i < p.n_items; i += (int)gridDim.x) {
         int t, c;
         g4k_item(p, i, t, c);
         if (t < p.n_tasks) break;
     }
     return i < p.n_items ? i : p.n_items;
+}
+template <class P>
+__device__ __forceinline__ int g4k_first_item(const P &p) { // workgroup entry: blockIdx.x, or the first item after it with a real task
+    int item = (int)blockIdx.x, t, c;
+    g4k_item(p, item, t, c);
+    if (t >= p.n_tasks) item = g4k_next_item(p, item);
+    return item;
+}
+// timeline (ps_hip_debug_timeline keys 48..50, 52) of a workgroup's slot: [0] / [31] entry / exit clock, [29] / [30] the same on the 100 MHz counter
+__device__ __forceinline__ void g4k_dbg_enter(unsigned long long *dbg) { if (dbg) { dbg[0] = __builtin_amdgcn_s_memtime(); dbg[29] = __builtin_amdgcn_s_memrealtime(); } }
+__device__ __forceinline__ void g4k_dbg_leave(unsigned long long *dbg) { if (dbg) { dbg[31] = __builtin_amdgcn_s_memtime(); dbg[30] = __builtin_amdgcn_s_memrealtime(); } }
+// workgroup entry of the staged kernels: the 32 zero bytes behind the stages (the zero operands; visible after the first barrier) and, EPI 1, the exp2 table at byte `tab`
+template <int EPI>
+__device__ __forceinline__ void g4k_lds_consts(char *lds, const int tab) {
+    if (threadIdx.x < 8) ((uint32_t *)(lds + G4K_NST * G4K_STAGE))[threadIdx.x] = 0u;
+    if (EPI == 1 && threadIdx.x >= 64 && threadIdx.x < 64 + PS_EXP2F_N) ((uint64_t *)(lds + tab))[threadIdx.x - 64] = ps_exp2f_tab[threadIdx.x - 64];
+}
+// lane m of column tile ct: its column, the column whose metadata it reads (the last tile may be ragged: clamped) and the tile it walks (a wave past the batch
+// walks the last tile's columns and stores nothing)
+struct G4KCols { int col, colc, ctc; };
+__device__ __forceinline__ G4KCols g4k_cols(const int ct, const int m, const int bs) {
+    const int col = ct * 16 + m;
+    return G4KCols{col, col < bs ? col : bs - 1, ct * 16 < bs ? ct : (bs - 1) / 16};
 }
 
 // The producers of a PERSISTENT workgroup: the stage stream runs on across the workgroup's items -- the ring is already
@@ -366,15 +417,11 @@ __device__ __forceinline__ void g4k_superblock(G4KAcc &T, const char *st, const 
         // mins lane v = kb's operand and the column's 16-sums 4 kb .. 4 kb + 3.  Half 0 keeps the chain (accm[.][.][0]).
         if (uh == 0) {
             const uint32_t bx = (kb & 1) ? M.b16.z : M.b16.x, by = (kb & 1) ? M.b16.w : M.b16.y; // (b16 = the 16 B holding lane kb's sums)
-            g4k_h2 g0, g1;
-            __builtin_memcpy(&g0, &bx, 4); __builtin_memcpy(&g1, &by, 4);
-            const g4k_h4 bm = {g0[0], g0[1], g1[0], g1[1]};
+            const g4k_h4 bm = g4k_h4_of(bx, by);
 #pragma unroll
             for (int t = 0; t < 2; t++) {
                 const uint2 ma = *(const uint2 *)(st + G4K_MINS + (16 * t + m) * 32 + kb * 8);
-                g4k_h2 a0, a1;
-                __builtin_memcpy(&a0, &ma.x, 4); __builtin_memcpy(&a1, &ma.y, 4);
-                const g4k_h4 am = {a0[0], a0[1], a1[0], a1[1]};
+                const g4k_h4 am = g4k_h4_of(ma.x, ma.y);
                 const g4k_f4 pr = __builtin_amdgcn_mfma_f32_16x16x16f16(am, bm, zf, 0, 0, 0);
                 T.accm[t][0][0] = T.accm[t][0][0] + dmin[t][0] * __builtin_shufflevector(pr, pr, 0, 1); // multiply, then add: two roundings (-ffp-contract=off)
                 T.accm[t][0][1] = T.accm[t][0][1] + dmin[t][1] * __builtin_shufflevector(pr, pr, 2, 3);
@@ -390,9 +437,7 @@ __device__ __forceinline__ void g4k_superblock(G4KAcc &T, const char *st, const 
 #pragma unroll
         for (int vv = 0; vv < 2; vv++) {
             const uint32_t ax = vv ? ma.z : ma.x, ay = vv ? ma.w : ma.y, bx = vv ? M.b16.z : M.b16.x, by = vv ? M.b16.w : M.b16.y;
-            g4k_h2 a0, a1, g0, g1;
-            __builtin_memcpy(&a0, &ax, 4); __builtin_memcpy(&a1, &ay, 4); __builtin_memcpy(&g0, &bx, 4); __builtin_memcpy(&g1, &by, 4);
-            const g4k_h4 am = {a0[0], a0[1], a1[0], a1[1]}, bm = {g0[0], g0[1], g1[0], g1[1]};
+            const g4k_h4 am = g4k_h4_of(ax, ay), bm = g4k_h4_of(bx, by);
             const g4k_f4 pr = __builtin_amdgcn_mfma_f32_16x16x16f16(am, bm, zf, 0, 0, 0);
             T.accm[t][vv][0] = __builtin_elementwise_fma(dmin[t][0], __builtin_shufflevector(pr, pr, 0, 1), T.accm[t][vv][0]);
             T.accm[t][vv][1] = __builtin_elementwise_fma(dmin[t][1], __builtin_shufflevector(pr, pr, 2, 3), T.accm[t][vv][1]);
@@ -407,29 +452,22 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm4k_kernel(const G4
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int m = lane & 15, kb = lane >> 4;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    if (threadIdx.x < 8) ((uint32_t *)(lds + G4K_NST * G4K_STAGE))[threadIdx.x] = 0u; // the zero operands (visible after the first barrier)
-    if (EPI == 1 && threadIdx.x >= 64 && threadIdx.x < 64 + PS_EXP2F_N) ((uint64_t *)(lds + G4K_TAB))[threadIdx.x - 64] = ps_exp2f_tab[threadIdx.x - 64];
-    int item = (int)blockIdx.x;
-    {
-        int t, c;
-        g4k_item(p, item, t, c);
-        if (t >= p.n_tasks) item = g4k_next_item(p, item);
-    }
+    g4k_lds_consts<EPI>(lds, G4K_TAB);
+    int item = g4k_first_item(p);
     if (item >= p.n_items) return; // (the whole workgroup)
-    // timeline: consumer wave 0 -> words 0..31, producer wave 8 -> 32..63 of the workgroup's slot ([0]/[31] entry / exit clock, [29]/[30] 100 MHz)
+    // timeline: consumer wave 0 -> words 0..31, producer wave 8 -> 32..63 of the workgroup's slot (text in both kernels: as a function the timeline build gets other scalar control flow)
     unsigned long long *const dbg = (PS_TL(p.dbg) && blockIdx.x < 1024 && lane == 0 && (wave == 0 || wave == G4K_NC)) ? p.dbg + ((size_t)blockIdx.x * 2 + (wave == G4K_NC)) * 32 : nullptr;
-    if (dbg) { dbg[0] = __builtin_amdgcn_s_memtime(); dbg[29] = __builtin_amdgcn_s_memrealtime(); }
+    g4k_dbg_enter(dbg);
     if (wave >= G4K_NC) {
         g4k_producer_wave<EPI, G4K_NP, G4K_RING, WT>(p, item, lds, wave - G4K_NC, dbg);
-        if (dbg) { dbg[31] = __builtin_amdgcn_s_memtime(); dbg[30] = __builtin_amdgcn_s_memrealtime(); }
+        g4k_dbg_leave(dbg);
         return;
     }
     const int ctl = wave & 3, uh = wave >> 2;
     int task, cb;
     g4k_item(p, item, task, cb);
-    const int ct = cb * 4 + ctl;
-    const int col = ct * 16 + m, colc = col < p.bs ? col : p.bs - 1; // (the last tile may be ragged: clamp the column metadata)
-    const int ctc = ct * 16 < p.bs ? ct : (p.bs - 1) / 16; // (a wave past the batch walks the last tile's columns and stores nothing)
+    const G4KCols C = g4k_cols(cb * 4 + ctl, m, p.bs);
+    const int col = C.col, colc = C.colc, ctc = C.ctc;
     const char *qf_ct = (const char *)p.qf + ((size_t)ctc * p.nsb << 13) + (size_t)(4 * uh) * 1024 + lane * 16;
     const uint8_t *mf_ct = p.mf + (size_t)ctc * p.nsb * 576;
     const int mc = colc & 15;
@@ -500,13 +538,12 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm4k_kernel(const G4
                     const float4 o4 = *(const float4 *)(theirs + (t * 2 + rr) * 4);
                     const float2 o2 = *(const float2 *)(theirs + 16 + (t * 2 + rr) * 2);
                     // lanes u < 4 (and mins lanes 0, 1) are half 0's, lanes u + 4 (mins 2, 3) half 1's
-                    const float s0 = __fadd_rn(G4K_OWN(a, 0), o4.x), s1 = __fadd_rn(G4K_OWN(a, 1), o4.y), s2 = __fadd_rn(G4K_OWN(a, 2), o4.z), s3 = __fadd_rn(G4K_OWN(a, 3), o4.w);
-                    const float res = __fadd_rn(__fadd_rn(s0, s2), __fadd_rn(s1, s3));
+                    const float res = g4k_hsum8(G4K_OWN(a, 0), G4K_OWN(a, 1), G4K_OWN(a, 2), G4K_OWN(a, 3), o4.x, o4.y, o4.z, o4.w);
                     const float w0 = G4K_OWN(am, 0), w1 = G4K_OWN(am, 1);
                     const float ma = uh ? o2.x : w0, mb = uh ? o2.y : w1;   // acc_m lanes 0, 1
                     const float mc2 = uh ? w0 : o2.x, md = uh ? w1 : o2.y;  // acc_m lanes 2, 3
 #undef G4K_OWN
-                    const float mm = WT == PS_Q5_K ? ma : __fadd_rn(__fadd_rn(ma, mc2), __fadd_rn(mb, md)); // (Q5_K: hsum_float_8(acc) + summs)
+                    const float mm = WT == PS_Q5_K ? ma : g4k_hsum4(ma, mb, mc2, md); // (Q5_K: hsum_float_8(acc) + summs)
                     y[t][rr] = __fadd_rn(res, mm);
                 }
             if (col < p.bs) {
@@ -515,8 +552,7 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm4k_kernel(const G4
                     const uint64_t *tab = (const uint64_t *)(lds + G4K_TAB);
                     float o[2];
 #pragma unroll
-                    for (int rr = 0; rr < 2; rr++) // ps_silu_mul with the table in LDS
-                        o[rr] = __fmul_rn(__fmul_rn(y[0][rr], __fdiv_rn(1.0f, __fadd_rn(1.0f, ps_expf_glibc(-y[0][rr], tab)))), y[1][rr]);
+                    for (int rr = 0; rr < 2; rr++) o[rr] = g4k_silu_mul(y[0][rr], y[1][rr], tab);
                     *(float2 *)(W.out + (int64_t)col * W.ldo + row0) = make_float2(o[0], o[1]);
                 } else {
 #pragma unroll
@@ -538,62 +574,56 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm4k_kernel(const G4
         mark(0);
         item = g4k_next_item(p, item);
     }
-    if (dbg) { dbg[31] = __builtin_amdgcn_s_memtime(); dbg[30] = __builtin_amdgcn_s_memrealtime(); }
+    g4k_dbg_leave(dbg);
 }
 
 // ---- narrow batches (at most 32 columns: tree verify, prompt tails).  With one or two live column tiles the wide mapping
 // leaves most consumers walking dead columns, and a consumer's step is a chain of LDS and L2 round trips (0.83 us) that does
-// not get shorter when others idle.  Here the eight consumers split ONE tile's work eight ways (CT = 1: wave = accumulator
-// lane u, waves 0..3 also mins lane v = u) or two tiles' four ways (CT = 2: two lanes u per wave, mins lane v = group): two
-// or four matrix instructions and a handful of chains per wave and step, and the B / column-metadata ring runs FOUR steps
-// ahead (a short step would otherwise wait for L2), so the workgroup runs at the producers' pace.  Same producers, same LDS
-// stages, same persistent items; every wave parks its chains at the end of an item and the waves of groups 0 and 1 finish
-// rows 4 kb + 0, 1 and 4 kb + 2, 3 (hsum_float_8's order) from LDS.
+// not get shorter when others idle.  Here the eight consumers split ONE tile's work eight ways (wave = accumulator lane u,
+// waves 0..3 also mins lane v = u): two matrix instructions and a handful of chains per wave and step, and the B /
+// column-metadata ring runs FOUR steps ahead (a short step would otherwise wait for L2), so the workgroup runs at the
+// producers' pace.  Same producers, same LDS stages, same persistent items; every wave parks its chains at the end of an
+// item and waves 0 and 1 finish rows 4 kb + 0, 1 and 4 kb + 2, 3 (hsum_float_8's order) from LDS.  (A two-tile form, CT = 2 --
+// two lanes u per wave on two column tiles -- spilled, 13.7 ms per 8B forward against 5.9 ms, and is gone; CT stays in the
+// parameter list for the instance names of the profile records.)
 constexpr int G4K_RINGN = 4; // (a ring of eight super-blocks measured slower: 12 wide 5.09 vs 4.78 ms)
 constexpr int G4K_NPN = 8; // producing waves of the narrow kernel: one accumulator lane each (the consumers are light there, the producers set the pace)
 template <int EPI, int CT, int WT>
 __global__ __launch_bounds__((G4K_NC + G4K_NPN) * 64) void gemm4k_narrow_kernel(const G4KParams p) {
-    constexpr int NU = CT, XW = CT == 1 ? 2 : 4; // accumulator lanes per wave; floats per (tile, row) in the exchange (NU chains + 1 mins chain, padded)
+    static_assert(CT == 1, "one column tile per workgroup");
+    constexpr int XW = 2; // floats per (tile, row) in the exchange: the wave's chain and its mins chain
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int m = lane & 15, kb = lane >> 4;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    if (threadIdx.x < 8) ((uint32_t *)(lds + G4K_NST * G4K_STAGE))[threadIdx.x] = 0u; // the zero operands (visible after the first barrier)
     constexpr int TAB = G4K_XCH + 8 * 64 * 8 * XW * 4;
-    if (EPI == 1 && threadIdx.x >= 64 && threadIdx.x < 64 + PS_EXP2F_N) ((uint64_t *)(lds + TAB))[threadIdx.x - 64] = ps_exp2f_tab[threadIdx.x - 64];
-    int item = (int)blockIdx.x;
-    {
-        int t, c;
-        g4k_item(p, item, t, c);
-        if (t >= p.n_tasks) item = g4k_next_item(p, item);
-    }
+    g4k_lds_consts<EPI>(lds, TAB);
+    int item = g4k_first_item(p);
     if (item >= p.n_items) return; // (the whole workgroup)
     unsigned long long *const dbg = (PS_TL(p.dbg) && blockIdx.x < 1024 && lane == 0 && (wave == 0 || wave == G4K_NC)) ? p.dbg + ((size_t)blockIdx.x * 2 + (wave == G4K_NC)) * 32 : nullptr;
-    if (dbg) { dbg[0] = __builtin_amdgcn_s_memtime(); dbg[29] = __builtin_amdgcn_s_memrealtime(); }
+    g4k_dbg_enter(dbg);
     if (wave >= G4K_NC) {
         g4k_producer_wave<EPI, G4K_NPN, G4K_RINGN, WT>(p, item, lds, wave - G4K_NC, dbg);
-        if (dbg) { dbg[31] = __builtin_amdgcn_s_memtime(); dbg[30] = __builtin_amdgcn_s_memrealtime(); }
+        g4k_dbg_leave(dbg);
         return;
     }
-    const int ctl = wave % CT, ug = wave / CT; // (column tile, accumulator-lane group: lanes u = NU ug .. NU ug + NU - 1)
-    const bool has_v = WT == PS_Q5_K ? ug == 0 : ug < 4; // mins lane v = ug (Q5_K: group 0 keeps the one scalar chain, k-group kb supplying lane v = kb)
+    const int ug = wave; // the wave's accumulator lane u
+    const bool has_v = WT == PS_Q5_K ? ug == 0 : ug < 4; // mins lane v = ug (Q5_K: wave 0 keeps the one scalar chain, k-group kb supplying lane v = kb)
     int task, cb;
     g4k_item(p, item, task, cb);
-    const int ct = cb * CT + ctl;
-    const int col = ct * 16 + m, colc = col < p.bs ? col : p.bs - 1;
-    const int ctc = ct * 16 < p.bs ? ct : (p.bs - 1) / 16;
-    const char *qf_ct = (const char *)p.qf + ((size_t)ctc * p.nsb << 13) + (size_t)(NU * ug) * 1024 + lane * 16;
+    const G4KCols C = g4k_cols(cb, m, p.bs); // (one column tile per block)
+    const int col = C.col, colc = C.colc, ctc = C.ctc;
+    const char *qf_ct = (const char *)p.qf + ((size_t)ctc * p.nsb << 13) + (size_t)ug * 1024 + lane * 16;
     const uint8_t *mf_ct = p.mf + (size_t)ctc * p.nsb * 576 + (colc & 15) * 4;                          // the column's scale
     const uint8_t *ms_ct = p.mf + (size_t)ctc * p.nsb * 576 + 64 + (colc & 15) * 32 + (WT == PS_Q5_K ? kb : (has_v ? ug : 0)) * 8; // the four 16-sums of mins lane v
     const char *zero = lds + G4K_NST * G4K_STAGE;
     float *xall = (float *)(lds + G4K_XCH);
     const g4k_f4 zf = {0.f, 0.f, 0.f, 0.f};
     // the ring: operands of the next four super-blocks
-    ps_u32x4 B[4][NU];
+    ps_u32x4 B[4];
     float yd[4];
     uint2 b16[4];
     auto ring_load = [&](const int j, const int sb) {
-#pragma unroll
-        for (int k = 0; k < NU; k++) B[j][k] = *(const ps_u32x4 *)(qf_ct + ((size_t)sb << 13) + k * 1024);
+        B[j] = *(const ps_u32x4 *)(qf_ct + ((size_t)sb << 13));
         yd[j] = *(const float *)(mf_ct + (size_t)sb * 576);
         b16[j] = *(const uint2 *)(ms_ct + (size_t)sb * 576);
     };
@@ -605,15 +635,11 @@ __global__ __launch_bounds__((G4K_NC + G4K_NPN) * 64) void gemm4k_narrow_kernel(
         int wi, pair;
         (void)g4k_rows<EPI>(p, task, wi, pair);
         const G4KMat &W = wi == 0 ? p.w[0] : (wi == 1 ? p.w[1] : p.w[2]);
-        float acc[2][4][NU], accm[2][4];
+        float acc[2][4], accm[2][4];
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) {
-#pragma unroll
-                for (int k = 0; k < NU; k++) acc[t][r][k] = 0.f;
-                accm[t][r] = 0.f;
-            }
+            for (int r = 0; r < 4; r++) acc[t][r] = accm[t][r] = 0.f;
 #pragma clang loop unroll(disable)
         for (int sb0 = 0; sb0 < p.nsb; sb0 += 4) {
 #pragma unroll
@@ -629,32 +655,25 @@ __global__ __launch_bounds__((G4K_NC + G4K_NPN) * 64) void gemm4k_narrow_kernel(
                     dr[t][0] = __fmul_rn(yd[j], dda[0]); dr[t][1] = __fmul_rn(yd[j], dda[2]); dr[t][2] = __fmul_rn(yd[j], ddb[0]); dr[t][3] = __fmul_rn(yd[j], ddb[2]);
                     dmin[t][0] = __fmul_rn(-yd[j], dda[1]); dmin[t][1] = __fmul_rn(-yd[j], dda[3]); dmin[t][2] = __fmul_rn(-yd[j], ddb[1]); dmin[t][3] = __fmul_rn(-yd[j], ddb[3]);
                 }
-                const char *ap = st + g4k_plane(kb) + m * G4K_RS + (NU * ug) * 16;
+                const char *ap = st + g4k_plane(kb) + m * G4K_RS + ug * 16;
+                g4k_h8 bv;
+                __builtin_memcpy(&bv, &B[j], 16);
 #pragma unroll
-                for (int k = 0; k < NU; k++) {
-                    g4k_h8 bv;
-                    __builtin_memcpy(&bv, &B[j][k], 16);
+                for (int t = 0; t < 2; t++) {
+                    const ps_u32x4 ao = *(const ps_u32x4 *)(ap + t * 16 * G4K_RS);
+                    g4k_h8 av;
+                    __builtin_memcpy(&av, &ao, 16);
+                    const g4k_f4 si = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, zf, 0, 0, 0);
 #pragma unroll
-                    for (int t = 0; t < 2; t++) {
-                        const ps_u32x4 ao = *(const ps_u32x4 *)(ap + t * 16 * G4K_RS + k * 16);
-                        g4k_h8 av;
-                        __builtin_memcpy(&av, &ao, 16);
-                        const g4k_f4 si = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, zf, 0, 0, 0);
-#pragma unroll
-                        for (int r = 0; r < 4; r++) acc[t][r][k] = __fmaf_rn(dr[t][r], si[r], acc[t][r][k]);
-                    }
+                    for (int r = 0; r < 4; r++) acc[t][r] = __fmaf_rn(dr[t][r], si[r], acc[t][r]);
                 }
                 { // (waves without a mins lane read the zero operands: their chains stay 0 and nobody reads them)
-                    g4k_h2 g0, g1;
-                    __builtin_memcpy(&g0, &b16[j].x, 4); __builtin_memcpy(&g1, &b16[j].y, 4);
-                    const g4k_h4 bm = {g0[0], g0[1], g1[0], g1[1]};
+                    const g4k_h4 bm = g4k_h4_of(b16[j].x, b16[j].y);
 #pragma unroll
                     for (int t = 0; t < 2; t++) {
                         const uint2 ma = *(const uint2 *)(WT == PS_Q5_K ? (has_v ? st + G4K_MINS + (16 * t + m) * 32 + kb * 8 : zero)
                                                                           : (kb == 0 && has_v ? st + G4K_MINS + (16 * t + m) * 32 + ug * 8 : zero));
-                        g4k_h2 a0, a1;
-                        __builtin_memcpy(&a0, &ma.x, 4); __builtin_memcpy(&a1, &ma.y, 4);
-                        const g4k_h4 am = {a0[0], a0[1], a1[0], a1[1]};
+                        const g4k_h4 am = g4k_h4_of(ma.x, ma.y);
                         const g4k_f4 pr = __builtin_amdgcn_mfma_f32_16x16x16f16(am, bm, zf, 0, 0, 0);
 #pragma unroll
                         for (int r = 0; r < 4; r++) accm[t][r] = WT == PS_Q5_K ? __fadd_rn(accm[t][r], __fmul_rn(dmin[t][r], pr[r])) : __fmaf_rn(dmin[t][r], pr[r], accm[t][r]);
@@ -664,16 +683,13 @@ __global__ __launch_bounds__((G4K_NC + G4K_NPN) * 64) void gemm4k_narrow_kernel(
                 nx = nx + 1 == p.nsb ? 0 : nx + 1;
             }
         }
-        // ---- every wave parks its chains; groups 0 and 1 finish rows 4 kb + 2 ug, + 1 of both tiles
+        // ---- every wave parks its chains; waves 0 and 1 finish rows 4 kb + 2 ug, + 1 of both tiles
         {
             float *mine = xall + ((size_t)wave * 64 + lane) * (8 * XW);
 #pragma unroll
             for (int t = 0; t < 2; t++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    if (NU == 1) *(float2 *)(mine + (t * 4 + r) * XW) = make_float2(acc[t][r][0], accm[t][r]);
-                    else *(float4 *)(mine + (t * 4 + r) * XW) = make_float4(acc[t][r][0], acc[t][r][NU - 1], accm[t][r], 0.f);
-                }
+                for (int r = 0; r < 4; r++) *(float2 *)(mine + (t * 4 + r) * XW) = make_float2(acc[t][r], accm[t][r]);
         }
         __syncthreads(); // X
         if (ug < 2) {
@@ -685,14 +701,11 @@ __global__ __launch_bounds__((G4K_NC + G4K_NPN) * 64) void gemm4k_narrow_kernel(
                     const int r = 2 * ug + rr;
                     float au[8], mv[4];
 #pragma unroll
-                    for (int u = 0; u < 8; u++) // lane u lives in wave (ctl, group u / NU), slot u % NU
-                        au[u] = xall[((size_t)(ctl + CT * (u / NU)) * 64 + lane) * (8 * XW) + (t * 4 + r) * XW + (u % NU)];
+                    for (int u = 0; u < 8; u++) au[u] = xall[((size_t)u * 64 + lane) * (8 * XW) + (t * 4 + r) * XW]; // lane u lives in wave u
 #pragma unroll
-                    for (int v = 0; v < 4; v++) // mins lane v lives in group v, after the NU chains
-                        mv[v] = xall[((size_t)(ctl + CT * v) * 64 + lane) * (8 * XW) + (t * 4 + r) * XW + NU];
-                    const float s0 = __fadd_rn(au[0], au[4]), s1 = __fadd_rn(au[1], au[5]), s2 = __fadd_rn(au[2], au[6]), s3 = __fadd_rn(au[3], au[7]);
-                    const float res = __fadd_rn(__fadd_rn(s0, s2), __fadd_rn(s1, s3));
-                    const float mm = WT == PS_Q5_K ? mv[0] : __fadd_rn(__fadd_rn(mv[0], mv[2]), __fadd_rn(mv[1], mv[3]));
+                    for (int v = 0; v < 4; v++) mv[v] = xall[((size_t)v * 64 + lane) * (8 * XW) + (t * 4 + r) * XW + 1]; // mins lane v in wave v, behind its chain
+                    const float res = g4k_hsum8(au[0], au[1], au[2], au[3], au[4], au[5], au[6], au[7]);
+                    const float mm = WT == PS_Q5_K ? mv[0] : g4k_hsum4(mv[0], mv[1], mv[2], mv[3]);
                     y[t][rr] = __fadd_rn(res, mm);
                 }
             if (col < p.bs) {
@@ -701,8 +714,7 @@ __global__ __launch_bounds__((G4K_NC + G4K_NPN) * 64) void gemm4k_narrow_kernel(
                     const uint64_t *tab = (const uint64_t *)(lds + TAB);
                     float o[2];
 #pragma unroll
-                    for (int rr = 0; rr < 2; rr++) // ps_silu_mul with the table in LDS
-                        o[rr] = __fmul_rn(__fmul_rn(y[0][rr], __fdiv_rn(1.0f, __fadd_rn(1.0f, ps_expf_glibc(-y[0][rr], tab)))), y[1][rr]);
+                    for (int rr = 0; rr < 2; rr++) o[rr] = g4k_silu_mul(y[0][rr], y[1][rr], tab);
                     *(float2 *)(W.out + (int64_t)col * W.ldo + row0) = make_float2(o[0], o[1]);
                 } else {
 #pragma unroll
@@ -715,14 +727,14 @@ __global__ __launch_bounds__((G4K_NC + G4K_NPN) * 64) void gemm4k_narrow_kernel(
                             if (W.bias) v[rr] = __fadd_rn(v[rr], W.bias[row0 + rr]);
                             if (p.residual && wi == 0) v[rr] = __fadd_rn(p.residual[(int64_t)col * W.ldo + row0 + rr], v[rr]);
                         }
-                        g4k_store_pair<2>(p, wi, W, col, row0, v[0], v[1]);
+                        g4k_store_pair<2>(p, wi, W, col, row0, v[0], v[1]); // (bias + residual + store stay text in every kernel: as one function the bias pair becomes one 8-byte load and this kernel takes 116 registers for 99)
                     }
                 }
             }
         }
         item = g4k_next_item(p, item);
     }
-    if (dbg) { dbg[31] = __builtin_amdgcn_s_memtime(); dbg[30] = __builtin_amdgcn_s_memrealtime(); }
+    g4k_dbg_leave(dbg);
 }
 
 // ================================================================ Q6_K (the Q4_K_M / Q5_K_M mixes: attn_v, half of the ffn_down, output)
@@ -749,18 +761,7 @@ struct G6KParams {
 constexpr int G6K_PLANE = 4 * G4K_KB + G4K_PAD, G6K_DD = 2 * G6K_PLANE, G6K_STAGE = G6K_DD + 32 * 4, G6K_NST = 2;
 constexpr int G6K_XCH = G6K_NST * G6K_STAGE, G6K_LDS = G6K_XCH + 2 * 4 * 64 * 16 * 4; // exchange: [half][column tile][lane][16 floats]
 
-__device__ __forceinline__ void g6k_item(const G6KParams &p, const int i, int &task, int &cb) {
-    cb = (i >> 3) % p.n_cb;
-    task = (i / (8 * p.n_cb)) * 8 + (i & 7);
-}
-__device__ __forceinline__ int g6k_next_item(const G6KParams &p, int i) {
-    for (i += (int)gridDim.x; i < p.n_items; i += (int)gridDim.x) {
-        int t, c;
-        g6k_item(p, i, t, c);
-        if (t < p.n_tasks) break;
-    }
-    return i < p.n_items ? i : p.n_items;
-}
+__device__ __forceinline__ void g4k_item(const G6KParams &p, const int i, int &task, int &cb) { g4k_item_rr(p.n_cb, i, task, cb); }
 
 // producer wave hw: accumulator lanes u = 2 hw, 2 hw + 1 of the 32 rows; lane = (row l / 2, half p = l % 2 of the super-block:
 // k-groups kb = 2p, 2p + 1 = vectors 4p .. 4p + 3)
@@ -809,7 +810,7 @@ __device__ __forceinline__ void g6k_producer_wave(const G6KParams &p, int item, 
     const uint8_t *qb, *hb, *sb_, *db;
     auto point = [&](int it) {
         int task, cb;
-        g6k_item(p, it, task, cb);
+        g4k_item(p, it, task, cb);
         const int64_t gr = (int64_t)task * 32 + row; // (two consecutive row tiles)
         qb = p.ql + (gr * nsb * 8 + 2 * hw) * 16 + pp * 8;
         hb = p.qh + (gr * nsb * 8 + 2 * hw) * 8 + pp * 4;
@@ -835,7 +836,7 @@ __device__ __forceinline__ void g6k_producer_wave(const G6KParams &p, int item, 
     while (item < p.n_items) {
         for (int g0 = 0; g0 < nsb; g0 += G4K_RING) {
             if (c_g == nsb) {
-                const int nx = g6k_next_item(p, c_item);
+                const int nx = g4k_next_item(p, c_item);
                 if (nx < p.n_items) { c_item = nx; c_g = 0; point(nx); } else c_g = nsb - G4K_RING;
             }
 #pragma unroll
@@ -852,7 +853,7 @@ __device__ __forceinline__ void g6k_producer_wave(const G6KParams &p, int item, 
             c_g += G4K_RING;
         }
         first = false;
-        item = g6k_next_item(p, item);
+        item = g4k_next_item(p, item);
     }
     __syncthreads(); // X of the last item
 }
@@ -861,20 +862,14 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm6k_kernel(const G6
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int m = lane & 15, kb = lane >> 4;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    int item = (int)blockIdx.x;
-    {
-        int t, c;
-        g6k_item(p, item, t, c);
-        if (t >= p.n_tasks) item = g6k_next_item(p, item);
-    }
+    int item = g4k_first_item(p);
     if (item >= p.n_items) return;
     if (wave >= G4K_NC) { g6k_producer_wave(p, item, lds, wave - G4K_NC); return; }
     const int ctl = wave & 3, uh = wave >> 2;
     int task, cb;
-    g6k_item(p, item, task, cb);
-    const int ct = cb * 4 + ctl;
-    const int col = ct * 16 + m, colc = col < p.bs ? col : p.bs - 1;
-    const int ctc = ct * 16 < p.bs ? ct : (p.bs - 1) / 16;
+    g4k_item(p, item, task, cb);
+    const G4KCols C = g4k_cols(cb * 4 + ctl, m, p.bs);
+    const int col = C.col, colc = C.colc, ctc = C.ctc;
     const char *qf_ct = (const char *)p.qf + ((size_t)ctc * p.nsb << 13) + (size_t)(4 * uh) * 1024 + lane * 16;
     const uint8_t *mf_ct = p.mf + (size_t)ctc * p.nsb * 576 + (colc & 15) * 4;
     float *xch = (float *)(lds + G6K_XCH) + ((size_t)ctl * 64 + lane) * 16;
@@ -884,7 +879,7 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm6k_kernel(const G6
     for (int k = 0; k < 4; k++) B[k] = *(const ps_u32x4 *)(qf_ct + k * 1024);
     float yd = *(const float *)mf_ct;
     while (item < p.n_items) {
-        g6k_item(p, item, task, cb);
+        g4k_item(p, item, task, cb);
         float acc[2][4][4];
 #pragma unroll
         for (int t = 0; t < 2; t++)
@@ -947,9 +942,8 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm6k_kernel(const G6
                     for (int rr = 0; rr < 2; rr++) {
                         const float4 o4 = *(const float4 *)(theirs + (t * 2 + rr) * 4);
 #define G6K_OWN(k) (uh ? acc[t][2 + rr][k] : acc[t][rr][k])
-                        const float s0 = __fadd_rn(G6K_OWN(0), o4.x), s1 = __fadd_rn(G6K_OWN(1), o4.y), s2 = __fadd_rn(G6K_OWN(2), o4.z), s3 = __fadd_rn(G6K_OWN(3), o4.w);
+                        v[rr] = g4k_hsum8(G6K_OWN(0), G6K_OWN(1), G6K_OWN(2), G6K_OWN(3), o4.x, o4.y, o4.z, o4.w);
 #undef G6K_OWN
-                        v[rr] = __fadd_rn(__fadd_rn(s0, s2), __fadd_rn(s1, s3));
                         if (p.bias) v[rr] = __fadd_rn(v[rr], p.bias[row0 + rr]);
                         if (p.residual) v[rr] = __fadd_rn(p.residual[(int64_t)col * p.ldo + row0 + rr], v[rr]);
                     }
@@ -957,7 +951,7 @@ __global__ __launch_bounds__((G4K_NC + G4K_NP) * 64) void gemm6k_kernel(const G6
                 }
             }
         }
-        item = g6k_next_item(p, item);
+        item = g4k_next_item(p, item);
     }
 }
 
@@ -1030,7 +1024,7 @@ __global__ __launch_bounds__(EPI == 1 ? 128 : 64, MB) void gemm4k_wav_kernel(con
         for (int v = 0; v < 4; v++) accm[r][v] = 0.f;
     }
     const g4k_f4 zf = {0.f, 0.f, 0.f, 0.f};
-    const g4k_h2 k1024 = {(_Float16)1024.f, (_Float16)1024.f}, km1024 = {(_Float16)-1024.f, (_Float16)-1024.f};
+    const g4k_h2 km1024 = {(_Float16)-1024.f, (_Float16)-1024.f};
     const uint32_t sel0 = 0x04000400u | ((uint32_t)(2 * (kb & 1)) * 0x00010001u), sel1 = sel0 + 0x00010001u; // scales 2 (kb & 1), + 1 of the four
 #pragma clang loop unroll(disable)
     for (int sb0 = 0; sb0 < nsb; sb0 += RA) { // (nsb % RA == 0: the host checks)
@@ -1040,19 +1034,17 @@ __global__ __launch_bounds__(EPI == 1 ? 128 : 64, MB) void gemm4k_wav_kernel(con
             const float yd = ryd[s & 1];
             const ps_u32x4 h = rh[s];
             // the scales of sub-blocks 2 kb, 2 kb + 1 (get_scale_min_k4) as fp16 pairs (s, s) and (-1024 s, -1024 s)
-            const uint32_t scb = (kb & 2) ? ((h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4)) : (h.y & 0x3f3f3f3fu);
-            const uint32_t t0 = __builtin_amdgcn_perm(0x64646464u, scb, sel0), t1 = __builtin_amdgcn_perm(0x64646464u, scb, sel1);
-            g4k_h2 s0, s1;
-            __builtin_memcpy(&s0, &t0, 4); __builtin_memcpy(&s1, &t1, 4);
-            s0 = s0 - k1024; s1 = s1 - k1024; // (bytes (s, 0x64) = fp16 1024 + s)
+            const uint32_t scb = g4k_scale_bytes(h, kb & 2);
+            const g4k_h2 s0 = g4k_byte_h2(scb, sel0), s1 = g4k_byte_h2(scb, sel1);
             const g4k_h2 n0 = s0 * km1024, n1 = s1 * km1024;
-            // d, dmin of the rows this lane's results belong to (rows 4 kb + r: their headers sit in lanes 4 kb + r)
+            // d, dmin of the rows this lane's results belong to (rows 4 kb + r: their headers sit in lanes 4 kb + r).  (The loop with its __shfl stays text here
+            // and in gemm4k_par_kernel: inside one function the EPI 1 instance came out with s_nop 17 -> 19 and a v_lshl_or_b32 for a shift and an or.)
             float dr[4], dmn[4];
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const uint32_t hx = (uint32_t)__shfl((int)h.x, 4 * kb + r, 64);
-                dr[r]  = __fmul_rn(yd, ps_h2f((uint16_t)(hx & 0xffff)));
-                dmn[r] = __fmul_rn(-yd, ps_h2f((uint16_t)(hx >> 16)));
+                dr[r]  = g4k_yd_d(hx, yd);
+                dmn[r] = g4k_yd_dmin(hx, yd);
             }
             // lane (r, u) parks its 16 bytes (dwords kb = 0 .. 3); lane (m, kb) picks dword kb of (row m, u) for the eight u.  One
             // wave, LDS operations in order: no barrier
@@ -1065,6 +1057,7 @@ __global__ __launch_bounds__(EPI == 1 ? 128 : 64, MB) void gemm4k_wav_kernel(con
             for (int u = 0; u < 8; u++) {
                 const uint32_t w = wq[u];
                 // nibble pairs as fp16 (1024 + n): (e0, e2), (e1, e3) of sub-block 2 kb, then of 2 kb + 1;  fma(1024 + n, s, -1024 s) = n s, exact
+                // (text here and in g4k_produce: as a function shared with it, equal mnemonic counts but this loop waits for its LDS reads elsewhere, down 12 wide 43.4 -> 43.6 us)
                 const uint32_t tq[4] = {(w & 0x000F000Fu) | 0x64006400u, ((w >> 8) & 0x000F000Fu) | 0x64006400u,
                                         ((w >> 4) & 0x000F000Fu) | 0x64006400u, ((w >> 12) & 0x000F000Fu) | 0x64006400u};
                 uint32_t o[4];
@@ -1085,16 +1078,12 @@ __global__ __launch_bounds__(EPI == 1 ? 128 : 64, MB) void gemm4k_wav_kernel(con
                 if (u & 1) __builtin_amdgcn_sched_barrier(0); // two accumulator lanes at a time: interleaving all eight costs registers, hides nothing other waves do not
             }
             { // the four mins lanes: A = (m[2v], m[2v], m[2v+1], m[2v+1]) in the lanes of k-group 0, zero elsewhere; B = the column's 16-sums
-                const uint32_t mn[2] = {h.z & 0x3f3f3f3fu, ((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4)};
+                const uint32_t mn[2] = {g4k_min_bytes(h, 0), g4k_min_bytes(h, 1)};
                 const uint32_t bw[8] = {rs[s & 1][0].x, rs[s & 1][0].y, rs[s & 1][0].z, rs[s & 1][0].w, rs[s & 1][1].x, rs[s & 1][1].y, rs[s & 1][1].z, rs[s & 1][1].w};
                 const g4k_h2 z2 = {(_Float16)0.f, (_Float16)0.f};
 #pragma unroll
                 for (int v = 0; v < 4; v++) {
-                    const uint32_t p0 = __builtin_amdgcn_perm(0x64646464u, mn[v >> 1], 0x04000400u | (uint32_t)(((2 * v) & 3) * 0x00010001u));
-                    const uint32_t p1 = __builtin_amdgcn_perm(0x64646464u, mn[v >> 1], 0x04000400u | (uint32_t)((((2 * v) & 3) + 1) * 0x00010001u));
-                    g4k_h2 h0, h1;
-                    __builtin_memcpy(&h0, &p0, 4); __builtin_memcpy(&h1, &p1, 4);
-                    h0 = h0 - k1024; h1 = h1 - k1024;
+                    g4k_h2 h0 = g4k_byte_h2(mn[v >> 1], 0x04000400u | (uint32_t)(((2 * v) & 3) * 0x00010001u)), h1 = g4k_byte_h2(mn[v >> 1], 0x04000400u | (uint32_t)((((2 * v) & 3) + 1) * 0x00010001u));
                     if (kb != 0) { h0 = z2; h1 = z2; }
                     const g4k_h4 am = {h0[0], h0[1], h1[0], h1[1]};
                     g4k_h4 bm;
@@ -1113,10 +1102,7 @@ __global__ __launch_bounds__(EPI == 1 ? 128 : 64, MB) void gemm4k_wav_kernel(con
     float y[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        const float s0 = __fadd_rn(acc[r][0], acc[r][4]), s1 = __fadd_rn(acc[r][1], acc[r][5]), s2 = __fadd_rn(acc[r][2], acc[r][6]), s3 = __fadd_rn(acc[r][3], acc[r][7]);
-        const float res = __fadd_rn(__fadd_rn(s0, s2), __fadd_rn(s1, s3));
-        const float mm = __fadd_rn(__fadd_rn(accm[r][0], accm[r][2]), __fadd_rn(accm[r][1], accm[r][3]));
-        y[r] = __fadd_rn(res, mm);
+        y[r] = __fadd_rn(g4k_hsum8(acc[r][0], acc[r][1], acc[r][2], acc[r][3], acc[r][4], acc[r][5], acc[r][6], acc[r][7]), g4k_hsum4(accm[r][0], accm[r][1], accm[r][2], accm[r][3]));
     }
     if constexpr (EPI == 1) { // wave 1 (the up tile) hands its rows to wave 0 (the gate tile)
         if (wave == 1) *(float4 *)(xup + lane * 4) = make_float4(y[0], y[1], y[2], y[3]);
@@ -1127,8 +1113,7 @@ __global__ __launch_bounds__(EPI == 1 ? 128 : 64, MB) void gemm4k_wav_kernel(con
             const int64_t row0 = (int64_t)task * 16 + kb * 4;
             float o[4];
 #pragma unroll
-            for (int r = 0; r < 4; r++) // ps_silu_mul with the table in LDS
-                o[r] = __fmul_rn(__fmul_rn(y[r], __fdiv_rn(1.0f, __fadd_rn(1.0f, ps_expf_glibc(-y[r], tab)))), uv[r]);
+            for (int r = 0; r < 4; r++) o[r] = g4k_silu_mul(y[r], uv[r], tab);
             *(float4 *)(W.out + (int64_t)col * W.ldo + row0) = make_float4(o[0], o[1], o[2], o[3]);
         }
     } else if (col < p.bs) {
@@ -1172,7 +1157,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm4k_par_kernel(const G4KParams p)
     unsigned long long *const dbg = (PS_TL(p.dbg) && blockIdx.x < 1024 && lane == 0 && wave == 0) ? p.dbg + (size_t)blockIdx.x * 64 : nullptr; // timeline (tools/par_timeline.py)
     int dbg_n = 1;
     auto mark = [&]() { if (dbg && dbg_n < 29) dbg[dbg_n++] = __builtin_amdgcn_s_memtime(); };
-    if (dbg) { dbg[0] = __builtin_amdgcn_s_memtime(); dbg[29] = __builtin_amdgcn_s_memrealtime(); }
+    g4k_dbg_enter(dbg);
     const int nsb = p.nsb;
     int wi, pair;
     const G4KRows R = g4k_rows<0>(p, (int)(blockIdx.x >> 1), wi, pair);
@@ -1240,7 +1225,8 @@ __global__ __launch_bounds__(NWV * 64) void gemm4k_par_kernel(const G4KParams p)
             {
                 const float yd = ryd[s & 1];
                 const ps_u32x4 h = rh[s];
-                const uint32_t scb = (kb & 2) ? ((h.w & 0x0f0f0f0fu) | (((h.y >> 6) & 0x03030303u) << 4)) : (h.y & 0x3f3f3f3fu);
+                const uint32_t scb = g4k_scale_bytes(h, kb & 2);
+                // (g4k_byte_h2's steps as text, here and at the mins below: through the function this kernel's loads are waited for elsewhere, s_waitcnt 151 -> 145 / 169 -> 168)
                 const uint32_t t0 = __builtin_amdgcn_perm(0x64646464u, scb, sel0), t1 = __builtin_amdgcn_perm(0x64646464u, scb, sel1);
                 g4k_h2 s0, s1;
                 __builtin_memcpy(&s0, &t0, 4); __builtin_memcpy(&s1, &t1, 4);
@@ -1251,8 +1237,8 @@ __global__ __launch_bounds__(NWV * 64) void gemm4k_par_kernel(const G4KParams p)
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const uint32_t hx = (uint32_t)__shfl((int)h.x, 4 * kb + r, 64);
-                    dr[r]  = __fmul_rn(yd, ps_h2f((uint16_t)(hx & 0xffff)));
-                    dmn[r] = __fmul_rn(-yd, ps_h2f((uint16_t)(hx >> 16)));
+                    dr[r]  = g4k_yd_d(hx, yd);
+                    dmn[r] = g4k_yd_dmin(hx, yd);
                 }
                 D[(wave * 2 + 0) * 64 + lane] = make_float4(dr[0], dr[1], dr[2], dr[3]);
                 D[(wave * 2 + 1) * 64 + lane] = make_float4(dmn[0], dmn[1], dmn[2], dmn[3]);
@@ -1286,7 +1272,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm4k_par_kernel(const G4KParams p)
                 }
                 mark(); // 3: accumulator lanes
                 {
-                    const uint32_t mn[2] = {h.z & 0x3f3f3f3fu, ((h.w >> 4) & 0x0f0f0f0fu) | (((h.z >> 6) & 0x03030303u) << 4)};
+                    const uint32_t mn[2] = {g4k_min_bytes(h, 0), g4k_min_bytes(h, 1)};
                     const uint32_t bw[8] = {rs[s & 1][0].x, rs[s & 1][0].y, rs[s & 1][0].z, rs[s & 1][0].w, rs[s & 1][1].x, rs[s & 1][1].y, rs[s & 1][1].z, rs[s & 1][1].w};
 #pragma unroll
                     for (int v = 0; v < 4; v++) {
@@ -1354,10 +1340,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm4k_par_kernel(const G4KParams p)
             for (int u = 0; u < 8; u++) au[u] = ((const float *)&S[u * 64 + lane])[r];
 #pragma unroll
             for (int q = 0; q < 4; q++) mq[q] = ((const float *)&M[q * 64 + lane])[r];
-            const float s0 = __fadd_rn(au[0], au[4]), s1 = __fadd_rn(au[1], au[5]), s2 = __fadd_rn(au[2], au[6]), s3 = __fadd_rn(au[3], au[7]);
-            const float res = __fadd_rn(__fadd_rn(s0, s2), __fadd_rn(s1, s3));
-            const float mm = __fadd_rn(__fadd_rn(mq[0], mq[2]), __fadd_rn(mq[1], mq[3]));
-            v[rr] = __fadd_rn(res, mm);
+            v[rr] = __fadd_rn(g4k_hsum8(au[0], au[1], au[2], au[3], au[4], au[5], au[6], au[7]), g4k_hsum4(mq[0], mq[1], mq[2], mq[3]));
         }
         const int64_t row0 = (int64_t)tile * 16 + kb * 4 + 2 * wave;
 #pragma unroll
@@ -1367,15 +1350,30 @@ __global__ __launch_bounds__(NWV * 64) void gemm4k_par_kernel(const G4KParams p)
         }
         g4k_store_pair<2>(p, wi, W, col, row0, v[0], v[1]);
     }
-    if (dbg) { dbg[31] = __builtin_amdgcn_s_memtime(); dbg[30] = __builtin_amdgcn_s_memrealtime(); }
+    g4k_dbg_leave(dbg);
 }
 constexpr int g4k_par_lds(const int nwv) { return nwv * ((8 + 4 + 2) * 64 * 16 + 16 * 36 * 4); }
 
-template <int EPI, int RA, int MB>
-static void g4k_launch_wav(hipStream_t st, const G4KParams &p) {
-    const unsigned grid = (unsigned)(EPI == 1 ? p.n_tasks : 2 * p.n_tasks);
-    psk_note_kernel("gemm4k_wav_kernel<%d, %d, %d>", EPI, RA, MB);
-    hipLaunchKernelGGL((gemm4k_wav_kernel<EPI, RA, MB>), dim3(grid), dim3(EPI == 1 ? 128 : 64), 0, st, p);
+// One launch: the instance and, beside it, the name psk_note_kernel records for it (ps_hip_last_matmul_kernel: the tests and bench.py's roofline read these strings)
+template <auto KERNEL, class P>
+static void g4k_run(const char *name, hipStream_t st, const int grid, const int block, const int lds, const P &p) {
+    psk_note_kernel("%s", name);
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3((unsigned)block), lds, st, p);
+}
+
+// The item plan of the staged kernels (Q4_K / Q5_K and Q6_K): ctw column tiles per workgroup give n_cb column blocks; items = (task, column block), the tasks padded
+// to a multiple of 8; n_wg workgroups.
+struct G4KPlan { int n_cb, n_items, n_wg; };
+static G4KPlan g4k_plan(const int n_cu, const int n_tasks, const int64_t bs, const int ctw) {
+    const int n_ct = (int)((bs + 15) / 16);
+    G4KPlan pl;
+    pl.n_cb = (n_ct + ctw - 1) / ctw;
+    pl.n_items = (n_tasks + 7) / 8 * 8 * pl.n_cb;
+    // persistent: one workgroup per CU walks the items w, w + n_wg, ... -- as long as that keeps its column block fixed
+    // (the consumers prefetch the next item's first fragments with this item's column pointers)
+    pl.n_wg = pl.n_items;
+    if (n_cu > 0 && pl.n_wg > n_cu && n_cu % (8 * pl.n_cb) == 0) pl.n_wg = n_cu;
+    return pl;
 }
 
 static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, const int64_t bs) {
@@ -1391,43 +1389,30 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
     // 32: 5.9, 64: 6.3, 128: 8.4 (wide); the round-1 kernels that spread a row group's integer work over producer waves
     // (gemm8): 2: 4.9, 8: 5.0, 12: 6.1, 16: 6.2, 32: 8.8, 64: 12.8, 96: 19.9.  These kernels take batches from PS_G4K_MIN_COLS columns on (psk_gemm4k_frag).
     const int par_cfg = g_g4k_par; // 0: off, 4 / 8: that many waves per tile, else by tile count
-    const int ctw = n_ct <= 1 ? 1 : 4; // column tiles per workgroup: the narrow kernel for at most 16 columns (its two-tile form, CT = 2, spills: 13.7 ms per 8B forward against 5.9 ms, not instantiated)
-    p.n_cb = (n_ct + ctw - 1) / ctw;
-    p.n_items = (p.n_tasks + 7) / 8 * 8 * p.n_cb;
-    // persistent: one workgroup per CU walks the items w, w + n_wg, ... -- as long as that keeps its column block fixed
-    // (the consumers prefetch the next item's first fragments with this item's column pointers)
-    int n_wg = p.n_items;
-    if (n_cu > 0 && n_wg > n_cu && n_cu % (8 * p.n_cb) == 0) n_wg = n_cu;
+    const int ctw = n_ct <= 1 ? 1 : 4; // column tiles per workgroup: the narrow kernel for at most 16 columns (its two-tile form, CT = 2, spilled, 13.7 ms per 8B forward against 5.9 ms, and is gone)
+    const G4KPlan pl = g4k_plan(n_cu, p.n_tasks, bs, ctw);
+    p.n_cb = pl.n_cb; p.n_items = pl.n_items;
+    const int n_wg = pl.n_wg;
     // the XCD-aware item order (g4k_item): column blocks per XCD; only where its arithmetic holds, else the round-2 order
     p.cbx = 0;
     static_assert(G4K_CBX > 0 && (G4K_CBX & (G4K_CBX - 1)) == 0, "a power of two");
     if (n_wg == 256 && p.n_items % 256 == 0 && (p.n_cb & (p.n_cb - 1)) == 0 && p.n_cb <= 8 && G4K_CBX < p.n_cb) p.cbx = G4K_CBX; // (cbx == n_cb IS the round-2 order)
-    const dim3 grid((unsigned)n_wg), blk((G4K_NC + G4K_NP) * 64), blkn((G4K_NC + G4K_NPN) * 64);
+    constexpr int blk = (G4K_NC + G4K_NP) * 64, blkn = (G4K_NC + G4K_NPN) * 64;
     static_assert(G4K_RING == 4, "nsb % 4 == 0 is what the producers' ring is unrolled for");
     constexpr int LDS1 = G4K_XCH + 8 * 64 * 8 * 2 * 4 + PS_EXP2F_N * 8;
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) {
-        (void)hipFuncSetAttribute((const void *)gemm4k_kernel<0, PS_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, G4K_LDS);
-        (void)hipFuncSetAttribute((const void *)gemm4k_kernel<1, PS_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, G4K_LDS);
-        (void)hipFuncSetAttribute((const void *)gemm4k_kernel<0, PS_Q5_K>, hipFuncAttributeMaxDynamicSharedMemorySize, G4K_LDS);
-        (void)hipFuncSetAttribute((const void *)gemm4k_narrow_kernel<0, 1, PS_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
-        (void)hipFuncSetAttribute((const void *)gemm4k_narrow_kernel<1, 1, PS_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
-        (void)hipFuncSetAttribute((const void *)gemm4k_narrow_kernel<0, 1, PS_Q5_K>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
-    }
+    ps_lds_opt_in<gemm4k_kernel<0, PS_Q4_K>, gemm4k_kernel<1, PS_Q4_K>, gemm4k_kernel<0, PS_Q5_K>>(G4K_LDS);
+    ps_lds_opt_in<gemm4k_narrow_kernel<0, 1, PS_Q4_K>, gemm4k_narrow_kernel<1, 1, PS_Q4_K>, gemm4k_narrow_kernel<0, 1, PS_Q5_K>>(LDS1);
     if (p.wt == PS_Q5_K) { // (single matrix, EPI 0)
-        if (ctw == 1) { psk_note_kernel("gemm4k_narrow_kernel<0, 1, 13>"); hipLaunchKernelGGL((gemm4k_narrow_kernel<0, 1, PS_Q5_K>), grid, blkn, LDS1, st, p); }
-        else { psk_note_kernel("gemm4k_kernel<0, 13>"); hipLaunchKernelGGL((gemm4k_kernel<0, PS_Q5_K>), grid, blk, G4K_LDS, st, p); }
+        if (ctw == 1) g4k_run<gemm4k_narrow_kernel<0, 1, PS_Q5_K>>("gemm4k_narrow_kernel<0, 1, 13>", st, n_wg, blkn, LDS1, p);
+        else g4k_run<gemm4k_kernel<0, PS_Q5_K>>("gemm4k_kernel<0, 13>", st, n_wg, blk, G4K_LDS, p);
     } else if (ctw == 1 && n_ct == 1 && epi != 1 && par_cfg != 0 && 2 * p.n_tasks < 4 * n_cu) {
         // at most 16 columns, few row tiles (Q / K / V, O, down of a tree batch): the super-blocks of a round side by side, the chains behind them
         // (any nsb).  8B, 12 wide, us per launch, four waves walking K -> this: see profiles/r04_tree12_kernel_stats.txt
-        static unsigned long long attrp = 0;
-        if (ps_first_on_device(&attrp)) {
-            (void)hipFuncSetAttribute((const void *)gemm4k_par_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, g4k_par_lds(8));
-            (void)hipFuncSetAttribute((const void *)gemm4k_par_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, g4k_par_lds(4));
-        }
+        ps_lds_opt_in<gemm4k_par_kernel<8>>(g4k_par_lds(8));
+        ps_lds_opt_in<gemm4k_par_kernel<4>>(g4k_par_lds(4));
         const int nwv = par_cfg == 4 || par_cfg == 8 ? par_cfg : (2 * p.n_tasks > n_cu ? 4 : 8); // more tiles than CUs: two workgroups of four waves per CU
-        if (nwv == 8) { psk_note_kernel("gemm4k_par_kernel<8>"); hipLaunchKernelGGL((gemm4k_par_kernel<8>), dim3((unsigned)(2 * p.n_tasks)), dim3(512), g4k_par_lds(8), st, p); }
-        else { psk_note_kernel("gemm4k_par_kernel<4>"); hipLaunchKernelGGL((gemm4k_par_kernel<4>), dim3((unsigned)(2 * p.n_tasks)), dim3(256), g4k_par_lds(4), st, p); }
+        if (nwv == 8) g4k_run<gemm4k_par_kernel<8>>("gemm4k_par_kernel<8>", st, 2 * p.n_tasks, 8 * 64, g4k_par_lds(8), p);
+        else g4k_run<gemm4k_par_kernel<4>>("gemm4k_par_kernel<4>", st, 2 * p.n_tasks, 4 * 64, g4k_par_lds(4), p);
     } else if (ctw == 1 && n_ct == 1 && p.nsb % 8 == 0) { // at most 16 columns: the wave-autonomous form
         // 8B tree forward 12 wide, us per launch, staged narrow kernel -> these (profiles/r03_tree12_kernel_stats*.txt): gate / up 39.6 -> 23.6,
         // Q / K / V and O 13 -> 11, down 31 -> 31, lm_head 151 -> 88; the forward 4.59 -> 3.68 ms.  Measured and not kept: the accumulator
@@ -1438,18 +1423,33 @@ static int g4k_launch(hipStream_t st, int n_cu, G4KParams &p, const int epi, con
         // header operands derived once by the parking wave instead of by all four (170 -> ~110 instructions per step: 16.6 us), a fifth
         // wave that owns the HBM stream with an eight-deep fragment ring in the others (22.9 us).
         // EPI 0 comes here with many tiles (lm_head: a wave per tile, occupancy hides the latency) and, A/B only, with few tiles under ps_hip_debug_set(3, 0)
-        if (epi == 1) g4k_launch_wav<1, 2, 2>(st, p);
-        else g4k_launch_wav<0, 2, 2>(st, p);
+        if (epi == 1) g4k_run<gemm4k_wav_kernel<1, 2, 2>>("gemm4k_wav_kernel<1, 2, 2>", st, p.n_tasks, 128, 0, p); // (a workgroup: the gate tile's wave and the up tile's)
+        else g4k_run<gemm4k_wav_kernel<0, 2, 2>>("gemm4k_wav_kernel<0, 2, 2>", st, 2 * p.n_tasks, 64, 0, p);
     } else if (ctw == 1) {
-        if (epi == 1) { psk_note_kernel("gemm4k_narrow_kernel<1, 1, 12>"); hipLaunchKernelGGL((gemm4k_narrow_kernel<1, 1, PS_Q4_K>), grid, blkn, LDS1, st, p); }
-        else { psk_note_kernel("gemm4k_narrow_kernel<0, 1, 12>"); hipLaunchKernelGGL((gemm4k_narrow_kernel<0, 1, PS_Q4_K>), grid, blkn, LDS1, st, p); }
-    } else if (epi == 1) { psk_note_kernel("gemm4k_kernel<1, 12>"); hipLaunchKernelGGL((gemm4k_kernel<1, PS_Q4_K>), grid, blk, G4K_LDS, st, p); }
-    else { psk_note_kernel("gemm4k_kernel<0, 12>"); hipLaunchKernelGGL((gemm4k_kernel<0, PS_Q4_K>), grid, blk, G4K_LDS, st, p); }
+        if (epi == 1) g4k_run<gemm4k_narrow_kernel<1, 1, PS_Q4_K>>("gemm4k_narrow_kernel<1, 1, 12>", st, n_wg, blkn, LDS1, p);
+        else g4k_run<gemm4k_narrow_kernel<0, 1, PS_Q4_K>>("gemm4k_narrow_kernel<0, 1, 12>", st, n_wg, blkn, LDS1, p);
+    } else if (epi == 1) g4k_run<gemm4k_kernel<1, PS_Q4_K>>("gemm4k_kernel<1, 12>", st, n_wg, blk, G4K_LDS, p);
+    else g4k_run<gemm4k_kernel<0, PS_Q4_K>>("gemm4k_kernel<0, 12>", st, n_wg, blk, G4K_LDS, p);
     return 0;
 }
 
 // Q4_K batched mat-mul from fragment-major Q8_K activations (act.qf).  With a.rope (a Q / K / V batch of at most 16 columns: the narrow
 // kernel) the epilogue rotates and appends to the KV cache: 8B tree forward 12 wide 4.72 -> 4.62 ms.
+// G4KParams of a launch but for the timeline slots and the RoPE epilogue: the matrices of `a` with the planes of their type (Q4_K: row-group units + headers; Q5_K: per-row
+// planes, headers and the fifth bits), tasks = pairs of row tiles (a SiLU pair: the gate tile and the up tile of the same rows)
+static G4KParams g4k_params(const psk_gemv_args &a, const ps_act act, const int64_t K, const int64_t bs, const int wt) {
+    G4KParams p{};
+    int pairs_total = 0;
+    for (int i = 0; i < a.n_w; i++) {
+        const ps_weight *w = a.w[i];
+        p.w[i] = G4KMat{w->qs, wt == PS_Q5_K ? w->sc : w->aux, wt == PS_Q5_K ? w->qh : nullptr, a.out[i], a.bias[i], w->N, a.ldo[i], (int)(w->N / 16)};
+        pairs_total += p.w[i].n_tiles / 2;
+    }
+    p.wt = wt; p.n_w = a.n_w; p.nsb = (int)(K / 256); p.bs = (int)bs;
+    p.n_tasks = a.silu_pair ? p.w[0].n_tiles : pairs_total;
+    p.residual = a.residual; p.qf = act.qf; p.mf = act.mf;
+    return p;
+}
 bool psk_gemm4k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
     if (a.pro != 0 || a.n_w < 1 || !psk_gemm4k_frag(K, bs)) return false;
     if (a.rope && (a.n_w != 3 || a.silu_pair || a.residual || bs > 16)) return false;
@@ -1458,18 +1458,9 @@ bool psk_gemm4k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
     return !a.silu_pair || (a.n_w == 2 && a.w[0]->N == a.w[1]->N && a.ldo[0] == a.ldo[1]);
 }
 int psk_gemm4k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
-    G4KParams p{};
-    int pairs_total = 0;
-    for (int i = 0; i < a.n_w; i++) {
-        p.w[i] = G4KMat{a.w[i]->qs, a.w[i]->aux, nullptr, a.out[i], a.bias[i], a.w[i]->N, a.ldo[i], (int)(a.w[i]->N / 16)};
-        pairs_total += p.w[i].n_tiles / 2;
-    }
+    G4KParams p = g4k_params(a, act, K, bs, PS_Q4_K);
     const int epi = a.silu_pair ? 1 : 0;
-    p.n_w = a.n_w; p.nsb = (int)(K / 256); p.bs = (int)bs;
-    p.n_tasks = epi == 1 ? p.w[0].n_tiles : pairs_total;
-    p.residual = a.residual; p.qf = act.qf; p.mf = act.mf;
     p.dbg = psk_gemv_dbg_buf(12 + epi, epi ? 0 : (a.n_w == 3 ? 0 : (K <= 8192 ? 1 : 2))); // keys 48 QKV, 49 O, 50 down, 52 gate/up
-    p.wt = PS_Q4_K;
     if (a.rope) { p.rope = *a.rope; p.rope_on = 1; }
     return g4k_launch(st, n_cu, p, epi, bs);
 }
@@ -1480,11 +1471,7 @@ bool psk_gemm5k_takes(const psk_gemv_args &a, int64_t K, int64_t bs) {
     return a.n_w == 1 && !a.silu_pair && w->dtype == PS_Q5_K && w->K == K && w->N % 32 == 0 && a.ldo[0] % 4 == 0 && psk_gemm4k_frag(K, bs);
 }
 int psk_gemm5k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K, int64_t bs) {
-    const ps_weight *w = a.w[0];
-    G4KParams p{};
-    p.w[0] = G4KMat{w->qs, w->sc, w->qh, a.out[0], a.bias[0], w->N, a.ldo[0], (int)(w->N / 16)};
-    p.n_w = 1; p.nsb = (int)(K / 256); p.bs = (int)bs; p.n_tasks = p.w[0].n_tiles / 2;
-    p.residual = a.residual; p.qf = act.qf; p.mf = act.mf; p.dbg = nullptr; p.wt = PS_Q5_K;
+    G4KParams p = g4k_params(a, act, K, bs, PS_Q5_K); // (no timeline slots)
     return g4k_launch(st, n_cu, p, 0, bs);
 }
 
@@ -1501,14 +1488,9 @@ int psk_gemm6k(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int
     p.out = a.out[0]; p.bias = a.bias[0]; p.residual = a.residual; p.N = w->N; p.ldo = a.ldo[0];
     p.nsb = (int)(K / 256); p.bs = (int)bs; p.n_tasks = (int)(w->N / 32);
     p.qf = act.qf; p.mf = act.mf;
-    const int n_ct = (int)((bs + 15) / 16);
-    p.n_cb = (n_ct + 3) / 4;
-    p.n_items = (p.n_tasks + 7) / 8 * 8 * p.n_cb;
-    int n_wg = p.n_items;
-    if (n_cu > 0 && n_wg > n_cu && n_cu % (8 * p.n_cb) == 0) n_wg = n_cu;
-    static unsigned long long attr = 0;
-    if (ps_first_on_device(&attr)) (void)hipFuncSetAttribute((const void *)gemm6k_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G6K_LDS);
-    psk_note_kernel("gemm6k_kernel");
-    hipLaunchKernelGGL(gemm6k_kernel, dim3((unsigned)n_wg), dim3((G4K_NC + G4K_NP) * 64), G6K_LDS, st, p);
+    const G4KPlan pl = g4k_plan(n_cu, p.n_tasks, bs, 4);
+    p.n_cb = pl.n_cb; p.n_items = pl.n_items;
+    ps_lds_opt_in<gemm6k_kernel>(G6K_LDS);
+    g4k_run<gemm6k_kernel>("gemm6k_kernel", st, pl.n_wg, (G4K_NC + G4K_NP) * 64, G6K_LDS, p);
     return 0;
 }

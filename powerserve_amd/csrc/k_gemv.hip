@@ -393,11 +393,8 @@ template <int WT, int UPW, int NW, int EPI, int PRO>
 void launch_g1(hipStream_t st, int n_cu, const GemvParams &p) {
     const int64_t n_tasks = (EPI == 1) ? p.w[0].n_groups : p.groups_total;
     const size_t smem     = (size_t)p.col_bytes;
-    static unsigned long long attr_set = 0; // devices that have the attribute
     static int occ = 0;
-    if (ps_first_on_device(&attr_set)) {
-        (void)hipFuncSetAttribute((const void *)gemv1_kernel<WT, UPW, NW, EPI, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    }
+    ps_lds_opt_in<gemv1_kernel<WT, UPW, NW, EPI, PRO>>(150 * 1024);
     if (occ == 0) { // resident workgroups per CU for this instantiation (registers / LDS), queried once
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)gemv1_kernel<WT, UPW, NW, EPI, PRO>, NW * 64, 24 * 1024) != hipSuccess || nb < 1) nb = 1;
@@ -444,10 +441,7 @@ void launch_one(hipStream_t st, int n_cu, const GemvParams &p) {
     const int64_t cap     = (int64_t)n_cu * (smem > 40 * 1024 ? 2 : 4);
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
-    static unsigned long long attr_set = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr_set) && smem > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void *)gemv_kernel<WT, BS, EPI, PRO, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    }
+    ps_lds_opt_in<gemv_kernel<WT, BS, EPI, PRO, NWV>>(160 * 1024 - 1024); // (whatever this launch's size: a later one of the instantiation may need it)
     psk_note_kernel("gemv_kernel<%d, %d, %d, %d, %d>", WT, BS, EPI, PRO, NWV);
     hipLaunchKernelGGL((gemv_kernel<WT, BS, EPI, PRO, NWV>), dim3((unsigned)grid), dim3(NWV * 64), smem, st, p);
 }
@@ -854,15 +848,13 @@ size_t psk_gemv_lds_col_bytes(int wt, int64_t K) {
 // Batched mat-mul from pre-quantized activations (Q4_K rows that psk_gemm4k_takes declines, Q4_0 / Q8_0 batches).
 template <int EPI, int NWV, int C>
 static void launch_gemm8m_k(hipStream_t st, const GemvParams &p, const dim3 grid, size_t smem) {
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) { (void)hipFuncSetAttribute((const void *)gemm8m_kernel<EPI, NWV, C>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); }
+    ps_lds_opt_in<gemm8m_kernel<EPI, NWV, C>>(159 * 1024);
     psk_note_kernel("gemm8m_kernel<%d, %d, %d>", EPI, NWV, C);
     hipLaunchKernelGGL((gemm8m_kernel<EPI, NWV, C>), grid, dim3(NWV * 64), smem, st, p);
 }
 template <int WT, int EPI, int NWV>
 static void launch_gemm8b_k(hipStream_t st, const GemvParams &p, const dim3 grid, size_t smem) {
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) { (void)hipFuncSetAttribute((const void *)gemm8b_kernel<WT, EPI, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); }
+    ps_lds_opt_in<gemm8b_kernel<WT, EPI, NWV>>(159 * 1024);
     psk_note_kernel("gemm8b_kernel<%d, %d, %d>", WT, EPI, NWV);
     hipLaunchKernelGGL((gemm8b_kernel<WT, EPI, NWV>), grid, dim3(NWV * 64), smem, st, p);
 }

@@ -364,10 +364,7 @@ template <int WT, int NW, int TPW, int EPI, int PRO>
 void launch_gb(hipStream_t st, int grid, const GBParams &p) {
     constexpr int UPB = NW * 2, RECF = GBT<WT>::RECF, RG = GBT<WT>::RG;
     const size_t smem = (size_t)p.act_bytes + (size_t)2 * UPB * RECF * 64 * sizeof(float4) + (size_t)3 * (p.split_q + 1) * RG * sizeof(float);
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) {
-        (void)hipFuncSetAttribute((const void *)gemvb_kernel<WT, NW, TPW, EPI, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    }
+    ps_lds_opt_in<gemvb_kernel<WT, NW, TPW, EPI, PRO>>(156 * 1024);
     psk_note_kernel("gemvb_kernel<%d, %d, %d, %d, %d>", WT, NW, TPW, EPI, PRO);
     hipLaunchKernelGGL((gemvb_kernel<WT, NW, TPW, EPI, PRO>), dim3((unsigned)grid), dim3((NW + 1) * 64), smem, st, p);
 }

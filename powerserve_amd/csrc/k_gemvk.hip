@@ -397,10 +397,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
 template <int WT, int NW, int UPW, int DC, int EA, int TPW, int EPI, int PRO>
 void launch_gk(hipStream_t st, int grid, const GKParams &p) {
     const size_t smem = (size_t)p.act_bytes + (size_t)2 * NW * UPW * 64 * sizeof(typename GKRec<WT>::T) + (size_t)3 * (p.split_q + 1) * 8 * sizeof(float);
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr) && smem > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void *)gemvk_kernel<WT, NW, UPW, DC, EA, TPW, EPI, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    }
+    ps_lds_opt_in<gemvk_kernel<WT, NW, UPW, DC, EA, TPW, EPI, PRO>>(128 * 1024);
     psk_note_kernel("gemvk_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", WT, NW, UPW, DC, EA, TPW, EPI, PRO);
     hipLaunchKernelGGL((gemvk_kernel<WT, NW, UPW, DC, EA, TPW, EPI, PRO>), dim3((unsigned)grid), dim3((NW + 1) * 64), smem, st, p);
 }

@@ -305,8 +305,7 @@ void psl_rope(hipStream_t st, const ps_tensor *dst, const ps_tensor *src, const 
 }
 void psl_softmax_ext(hipStream_t st, const ps_tensor *dst, const ps_tensor *src, const float *mask, float scale) {
     const int64_t rows = src->ne[1] * src->ne[2] * src->ne[3];
-    static unsigned long long attr = 0; // devices that have the attribute (rows of more than 64 KiB)
-    if (ps_first_on_device(&attr)) (void)hipFuncSetAttribute((const void *)softmax_ext_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+    ps_lds_opt_in<softmax_ext_kernel>(152 * 1024); // (rows of more than 64 KiB)
     hipLaunchKernelGGL(softmax_ext_kernel, dim3((unsigned)rows), dim3(256), (size_t)src->ne[0] * 4, st, tdesc(dst),
                        tdesc(src), mask, scale);
 }

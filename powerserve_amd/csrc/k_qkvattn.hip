@@ -694,13 +694,7 @@ bool psk_qkv_attn(hipStream_t st, int n_cu, const psk_gemv_args &g, int64_t K, c
     p.gran = g_qa_counter ? nullptr : a.gran;
     const size_t lds = qa_lds_bytes(p, hs);
     if (lds > 160 * 1024) return false;
-    static unsigned long long attr = 0;
-    if (ps_first_on_device(&attr)) {
-        (void)hipFuncSetAttribute((const void *)qkv_attn_kernel<4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)qkv_attn_kernel<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)qkv_attn_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)qkv_attn_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
+    ps_lds_opt_in<qkv_attn_kernel<4, 0>, qkv_attn_kernel<2, 0>, qkv_attn_kernel<4, 1>, qkv_attn_kernel<2, 1>>(160 * 1024);
     const dim3 grid((unsigned)(G * a.n_kv_heads));
     psk_note_attn("qkv_attn_kernel<%d, %d>", hs / 32, a.kv_stream ? 1 : 0);
     if (hs == 128) { if (a.kv_stream) hipLaunchKernelGGL((qkv_attn_kernel<4, 1>), grid, dim3(QA_THREADS), lds, st, p); else hipLaunchKernelGGL((qkv_attn_kernel<4, 0>), grid, dim3(QA_THREADS), lds, st, p); }

@@ -368,11 +368,8 @@ int psf16_gemm_n(ps_hip_ctx *c, psf16 *, int n_w, const _Float16 *const *W, cons
         for (int i = 0; i < n_w; i++) if (N[i] % bn) PS_FAIL(c, "fp16 perf mode: the large-tile GEMM needs rows in multiples of its tile");
         p.n_tm = n_tm_big;
         for (int i = 0; i < n_w; i++) { p.w[i] = F16Mat{W[i], out[i], N[i], ldo[i], (int)(N[i] / bn)}; p.tiles_total += p.w[i].tiles; }
-        static unsigned long long attrd = 0;
-        if (ps_first_on_device(&attrd)) {
-            (void)hipFuncSetAttribute((const void *)f16_gemm_w8_kernel<2, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 256) * 128);
-            (void)hipFuncSetAttribute((const void *)f16_gemm_w8_kernel<4, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 128) * 128);
-        }
+        ps_lds_opt_in<f16_gemm_w8_kernel<2, 4, 2>>(2 * (256 + 256) * 128);
+        ps_lds_opt_in<f16_gemm_w8_kernel<4, 2, 2>>(2 * (256 + 128) * 128);
         const dim3 grid((unsigned)((p.tiles_total + 7) / 8 * 8 * p.n_tm));
         if (nj == 4) hipLaunchKernelGGL((f16_gemm_w8_kernel<2, 4, 2>), grid, dim3(512), 2 * (256 + 256) * 128, c->stream, p);
         else hipLaunchKernelGGL((f16_gemm_w8_kernel<4, 2, 2>), grid, dim3(512), 2 * (256 + 128) * 128, c->stream, p);
@@ -385,11 +382,8 @@ int psf16_gemm_n(ps_hip_ctx *c, psf16 *, int n_w, const _Float16 *const *W, cons
     for (int i = 0; i < n_w; i++) { p.w[i] = F16Mat{W[i], out[i], N[i], ldo[i], (int)(N[i] / bn)}; p.tiles_total += p.w[i].tiles; }
     const unsigned grid = (unsigned)((p.tiles_total + 7) / 8 * 8 * p.n_tm);
     const size_t smem = (size_t)2 * (F16_BM + bn) * F16_RS;
-    static unsigned long long attr = 0; // devices that have the attribute
-    if (ps_first_on_device(&attr)) {
-        (void)hipFuncSetAttribute((const void *)f16_gemm_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (F16_BM + 128) * F16_RS);
-        (void)hipFuncSetAttribute((const void *)f16_gemm_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (F16_BM + 64) * F16_RS);
-    }
+    ps_lds_opt_in<f16_gemm_kernel<128>>(2 * (F16_BM + 128) * F16_RS);
+    ps_lds_opt_in<f16_gemm_kernel<64>>(2 * (F16_BM + 64) * F16_RS);
     if (bn == 128) hipLaunchKernelGGL(f16_gemm_kernel<128>, dim3(grid), dim3(256), smem, c->stream, p);
     else hipLaunchKernelGGL(f16_gemm_kernel<64>, dim3(grid), dim3(256), smem, c->stream, p);
     PS_CHECK(c, hipGetLastError());

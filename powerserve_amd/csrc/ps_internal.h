@@ -75,23 +75,17 @@ struct ps_act {
                  // (int16): a wave of the Q4_K batched mat-mul reads its 16 columns' scale and sums from 5 cache lines, not 48
 };
 
-// hipFuncSetAttribute is per device: `mask` (one static per kernel instantiation) remembers the devices that have it
-static inline bool ps_first_on_device(unsigned long long *mask) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (*mask & bit) return false;
-    *mask |= bit;
-    return true;
-}
-
-// Opt KERNELS in to `bytes` of dynamic LDS (above the 64 KiB a kernel gets unasked), once per device; one call site per set of kernels.  True: this was the
-// first call on the current device.
+// Opt KERNELS in to `bytes` of dynamic LDS (above the 64 KiB a kernel gets unasked), once per device and whatever the size of the launch that comes first (a later
+// launch of the same instantiation may need it); one call site per set of kernels.  True: this was the first call on the current device.
 constexpr int PS_LDS_MAX = 156 * 1024; // what the large attention kernels ask for
 template <auto... KERNELS>
 static inline bool ps_lds_opt_in(const int bytes = PS_LDS_MAX) {
-    static unsigned long long done = 0; // devices that have the attribute
-    if (!ps_first_on_device(&done)) return false;
+    static unsigned long long done = 0; // hipFuncSetAttribute is per device: the devices that have it (one mask per set of kernels)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done & bit) return false;
+    done |= bit;
     ((void)hipFuncSetAttribute((const void *)KERNELS, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), ...);
     return true;
 }

@@ -171,6 +171,7 @@ def lib() -> C.CDLL:
         "ps_hip_model_kv_append_tokens": (i32, [vp, sz, C.POINTER(sz)]), "ps_hip_model_argmax": (i32, [vp, i32, vp]),
         "ps_hip_debug_timeline": (i32, [vp, i32, vp, i32]),
         "ps_hip_last_matmul_kernel": (C.c_char_p, []),
+        "ps_hip_model_bench_matmul": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
         "ps_hip_last_attention_kernel": (C.c_char_p, []),
         "ps_hip_debug_set": (i32, [i32, i32]),
         "ps_hip_sample_covered": (i32, [vp, i32, vp]), "ps_hip_sample": (i32, [vp, vp, i32, vp, vp, vp]),

@@ -35,6 +35,10 @@ PRESETS = {
     "tiny-qwen2-v1000": ("qwen2", 256, 512, 2, 4, 2, 64, 1000, 1e6, 2, True, 1e-6),
     "small-llama": ("llama", 512, 1536, 3, 8, 2, 64, 2048, 5e5, 0, True, 1e-5),
     "small-llama-hs128": ("llama", 1024, 2048, 2, 8, 2, 128, 1024, 5e5, 0, False, 1e-5),
+    # Qwen2 (Q / K / V bias) at widths that are multiples of 1024, which the chunk mat-mul (k_gemm4k.hip) needs: K / 256 = 4 (its narrow kernel below 17 columns), and
+    # 8 / 12 (the wave-autonomous kernel; ragged rounds of the round-parallel one and the narrow kernel on the down projection)
+    "small-qwen2-hs128": ("qwen2", 1024, 2048, 2, 8, 2, 128, 1024, 1e6, 2, True, 1e-6),
+    "wide-qwen2-hs128": ("qwen2", 2048, 3072, 2, 16, 4, 128, 1024, 1e6, 2, True, 1e-6),
     # a draft model for small-llama-hs128: same vocabulary, different width / depth / head size
     "small-llama-draft": ("llama", 512, 1024, 3, 8, 4, 64, 1024, 5e5, 0, True, 1e-5),
     # the headline's depth behind a long cache at a width the CPU oracle finishes in seconds (tests/test_gpu_fullsize.py)

@@ -369,6 +369,59 @@ def test_wide_prefill_chunks_match_oracle(ctx, oracle, tmp_path, preset, wt, chu
     om.close()
 
 
+# (batch, ps_hip_debug_set(3, .), launch group of ps_hip_model_bench_matmul: 2 Q / K / V, 1 gate / up, 4 down) -> the kernel k_gemm4k.hip's launcher picks on 256 CUs
+G4K_DIM1024 = {(40, 1, 2): "gemm4k_kernel<0, 12>", (40, 1, 1): "gemm4k_kernel<1, 12>", (12, 1, 2): "gemm4k_par_kernel<8>",
+               (12, 1, 1): "gemm4k_narrow_kernel<1, 1, 12>", (12, 0, 2): "gemm4k_narrow_kernel<0, 1, 12>"}
+G4K_DIM2048 = {(12, 0, 2): "gemm4k_wav_kernel<0, 2, 2>", (12, 0, 4): "gemm4k_narrow_kernel<0, 1, 12>",
+               (12, 1, 1): "gemm4k_wav_kernel<1, 2, 2>", (12, 0, 1): "gemm4k_wav_kernel<1, 2, 2>"}
+
+
+@pytest.mark.parametrize("preset,kernels", [("small-qwen2-hs128", G4K_DIM1024), ("wide-qwen2-hs128", G4K_DIM2048), ("small-llama-hs128", G4K_DIM1024)])
+def test_chunk_matmul_forms_match_oracle(ctx, oracle, tmp_path, preset, kernels):
+    """Every form of the Q4_K chunk mat-mul (k_gemm4k.hip: wide, narrow, wave-autonomous, round-parallel) inside a model: batches of 40, 12, 5, 2 and 1
+    tokens, logits of every batch and layer 0's K / V cache bit-equal to the oracle, by default and with the round-parallel form switched off
+    (ps_hip_debug_set(3, 0): its launches go to the narrow and the wave-autonomous kernels).  The Qwen2 presets carry a Q / K / V bias through all
+    four kernels, the Llama preset the RoPE + KV-append epilogue through the round-parallel and the narrow one; the replay of a layer's launches
+    names the kernel that served them."""
+    import ctypes as C
+    from oracle import binding as B
+    from powerserve_amd import hip, synth
+    d = str(tmp_path / "m")
+    mj = synth.write_model_dir(d, preset, 12, n_ctx=256, seed=17)
+    cfg = B.make_config(mj["llm_config"])
+    om = oracle.model(cfg, mj["model_arch"], load_tensors(os.path.join(d, "ggml/weights.gguf")), n_threads=16)
+    batches = (40, 12, 5, 2, 1)
+    toks = np.random.default_rng(23).integers(0, cfg.vocab_size, sum(batches))
+    want, done = [], 0
+    for bs in batches:
+        want.append(om.forward(toks[done:done + bs], np.arange(done, done + bs), True))
+        done += bs
+    want_k, want_v = om.k_cache(0)[:done].copy(), om.v_cache(0)[:, :done].copy()
+    om.close()
+    gm = hip.Model(ctx, d, max_batch=64, n_ctx=256)
+    seen = {}
+    try:
+        for par in (1, 0):
+            assert ctx.L.ps_hip_debug_set(3, par) == 0
+            gm.reset()
+            done = 0
+            for bs, w in zip(batches, want):
+                got, _ = gm.forward(toks[done:done + bs], np.arange(done, done + bs), True)
+                assert np.array_equal(got.view(np.uint32), w.view(np.uint32)), (par, bs, rel_err(got, w))
+                done += bs
+                for which in (2, 1, 4):
+                    seq_ms, null_ms, n = C.c_double(), C.c_double(), C.c_int()
+                    ctx.check(ctx.L.ps_hip_model_bench_matmul(gm.h, 1, which, bs, C.byref(seq_ms), C.byref(null_ms), C.byref(n)))
+                    seen[(bs, par, which)] = ctx.L.ps_hip_last_matmul_kernel().decode()
+            assert np.array_equal(gm.k_cache(0)[:done].view(np.uint32), want_k.view(np.uint32)), par
+            assert np.array_equal(gm.v_cache(0)[:, :done].view(np.uint32), want_v.view(np.uint32)), par
+    finally:
+        ctx.L.ps_hip_debug_set(3, 1)
+    print(preset, seen)
+    assert {k: seen[k] for k in kernels} == kernels
+    gm.close()
+
+
 @pytest.mark.parametrize("wt", [12, 1015, 1017])  # pure Q4_K; the Q4_K_M mix (Q6_K attn_v / ffn_down / output: the prefill chunks take gemm6k); Q5_K_M (Q5_K producer + gemm6k)
 def test_long_context_batches_match_oracle(ctx, oracle, tmp_path, wt):
     """Batches appended behind a long KV prefix (n_kv > 256: several 32-column chain rounds, leftovers, softmax tails):

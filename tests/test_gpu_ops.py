@@ -143,6 +143,25 @@ def test_mul_mat_fallback_routes(ctx, oracle, hip, wt, K, N, bs, kernel):
     W.free()
 
 
+def test_mul_mat_small_rows_then_rows_past_64k_of_lds(ctx, oracle, hip):
+    """One instantiation, gemv_kernel<8, 4, 0, 0, 4>, first with a column image far below 64 KiB of LDS (K = 160) and then above it (K = 12320: four
+    columns of 17 072 bytes = 68 288): the opt-in to more than 64 KiB belongs to the kernel, not to the size of its first launch, so the second
+    launch runs -- both bit-equal to the oracle."""
+    from powerserve_amd import synth
+    for K in (160, 12320):  # (12320 % 128 = 32: the partial last unit of the 160 case)
+        rng = np.random.default_rng(8 * 131 + K)
+        w = synth.random_blocks(rng, 8, 24, K)
+        x = (rng.standard_normal((3, K)) * rng.uniform(0.1, 30.0, (3, 1))).astype(np.float32)
+        want = oracle.mul_mat(8, w, K, 24, x)
+        W = ctx.upload_weight(8, w, K, 24)
+        dx, dy = ctx.to_device(x), ctx.empty((3, 24))
+        ctx.check(ctx.L.ps_hip_mul_mat(ctx.h, C.byref(dy.tensor()), C.byref(W.tensor()), C.byref(dx.tensor())))
+        assert ctx.L.ps_hip_last_matmul_kernel().decode() == "gemv_kernel<8, 4, 0, 0, 4>", K
+        got = dy.numpy()
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (K, rel_err(got, want), np.argwhere(got != want)[:8])
+        W.free()
+
+
 @pytest.mark.parametrize("K,N,bs", [(4096, 512, 128), (1024, 96, 120), (14336, 64, 113), (2048, 288, 128), (1024, 64, 160), (2048, 96, 200), (1024, 8224, 70), (1024, 32, 12), (4096, 160, 2), (2048, 8224, 16), (1024, 64, 5)])
 def test_mul_mat_q4k_chunk_on_matrix_cores(ctx, oracle, hip, K, N, bs):
     """Batches of a Q4_K weight from 2 columns (N % 32 == 0, K % 1024 == 0) take k_gemm4k.hip (17 and more: the wide kernel, fewer: the narrow one): fp16 MFMA contractions of
