@@ -115,7 +115,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const GemvParams p) {
             if (EPI == 1) {
                 wi = pass;
             } else {
-                if (p.n_w > 1 && grp >= p.w[0].n_groups) { grp -= p.w[0].n_groups; wi = 1; }
+                if (p.n_w > 1 && grp >= p.w[0].n_groups) { grp -= p.w[0].n_groups; wi = 1; } // (ch_mat_select's walk, 64-bit: text at the five sites of this file -- 48 of its 95 symbols changed through the function)
                 if (p.n_w > 2 && wi == 1 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; wi = 2; }
             }
             const GemvW &W    = p.w[wi];
@@ -404,8 +404,8 @@ void launch_g1(hipStream_t st, int n_cu, const GemvParams &p) {
     const int64_t cap = (int64_t)n_cu * occ;
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
-    psk_note_kernel("gemv1_kernel<%d, %d, %d, %d, %d>", WT, UPW, NW, EPI, PRO);
-    hipLaunchKernelGGL((gemv1_kernel<WT, UPW, NW, EPI, PRO>), dim3((unsigned)grid), dim3(NW * 64), smem, st, p);
+    // (opted in above, ahead of the occupancy query)
+    ps_run<gemv1_kernel<WT, UPW, NW, EPI, PRO>>(st, dim3((unsigned)grid), NW * 64, smem, 0, p, "gemv1_kernel<%d, %d, %d, %d, %d>", WT, UPW, NW, EPI, PRO);
 }
 
 template <int WT, int UPW, int NW>
@@ -441,9 +441,7 @@ void launch_one(hipStream_t st, int n_cu, const GemvParams &p) {
     const int64_t cap     = (int64_t)n_cu * (smem > 40 * 1024 ? 2 : 4);
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
-    ps_lds_opt_in<gemv_kernel<WT, BS, EPI, PRO, NWV>>(160 * 1024 - 1024); // (whatever this launch's size: a later one of the instantiation may need it)
-    psk_note_kernel("gemv_kernel<%d, %d, %d, %d, %d>", WT, BS, EPI, PRO, NWV);
-    hipLaunchKernelGGL((gemv_kernel<WT, BS, EPI, PRO, NWV>), dim3((unsigned)grid), dim3(NWV * 64), smem, st, p);
+    ps_run<gemv_kernel<WT, BS, EPI, PRO, NWV>>(st, dim3((unsigned)grid), NWV * 64, smem, 160 * 1024 - 1024, p, "gemv_kernel<%d, %d, %d, %d, %d>", WT, BS, EPI, PRO, NWV);
 }
 
 // (psk_gemv_takes: a SiLU pair never comes with the plain quantizer prologue, 2..4 columns always come pre-quantized)
@@ -848,15 +846,11 @@ size_t psk_gemv_lds_col_bytes(int wt, int64_t K) {
 // Batched mat-mul from pre-quantized activations (Q4_K rows that psk_gemm4k_takes declines, Q4_0 / Q8_0 batches).
 template <int EPI, int NWV, int C>
 static void launch_gemm8m_k(hipStream_t st, const GemvParams &p, const dim3 grid, size_t smem) {
-    ps_lds_opt_in<gemm8m_kernel<EPI, NWV, C>>(159 * 1024);
-    psk_note_kernel("gemm8m_kernel<%d, %d, %d>", EPI, NWV, C);
-    hipLaunchKernelGGL((gemm8m_kernel<EPI, NWV, C>), grid, dim3(NWV * 64), smem, st, p);
+    ps_run<gemm8m_kernel<EPI, NWV, C>>(st, grid, NWV * 64, smem, 159 * 1024, p, "gemm8m_kernel<%d, %d, %d>", EPI, NWV, C);
 }
 template <int WT, int EPI, int NWV>
 static void launch_gemm8b_k(hipStream_t st, const GemvParams &p, const dim3 grid, size_t smem) {
-    ps_lds_opt_in<gemm8b_kernel<WT, EPI, NWV>>(159 * 1024);
-    psk_note_kernel("gemm8b_kernel<%d, %d, %d>", WT, EPI, NWV);
-    hipLaunchKernelGGL((gemm8b_kernel<WT, EPI, NWV>), grid, dim3(NWV * 64), smem, st, p);
+    ps_run<gemm8b_kernel<WT, EPI, NWV>>(st, grid, NWV * 64, smem, 159 * 1024, p, "gemm8b_kernel<%d, %d, %d>", WT, EPI, NWV);
 }
 template <int WT>
 static int launch_gemm8(hipStream_t st, const GemvParams &p, int epi, int nwv, const dim3 grid, size_t smem) {

@@ -110,7 +110,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
         int tS[DC], uS[DC];
 #pragma unroll
         for (int d = 0; d < DC; d++) {
-            int t = 0, un = d * UPB + wave * UPW;
+            int t = 0, un = d * UPB + wave * UPW; // (text: through ch_slot_init the eight NW = 7 instances get other scalar code, s_add_i32 58 -> 60 and on)
             while (un >= tot) { un -= tot; t++; }
             tS[d] = t; uS[d] = un;
         }
@@ -129,7 +129,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
             const uint8_t *qb = p.w[0].qs, *ab = p.w[0].aux;
             if (EPI == 1) {
                 if (ul >= n_units) { ul -= n_units; qb = p.w[1].qs; ab = p.w[1].aux; }
-            } else if (p.n_w > 1 && grp >= p.w[0].n_groups) {
+            } else if (p.n_w > 1 && grp >= p.w[0].n_groups) { // (ch_mat_select's walk with the pointer picks inside it: text here and in gemvb -- through the function 32 instances of each trade scalar branches for selects)
                 grp -= p.w[0].n_groups; qb = p.w[1].qs; ab = p.w[1].aux;
                 if (p.n_w > 2 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; qb = p.w[2].qs; ab = p.w[2].aux; }
             }
@@ -154,10 +154,6 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
                                                                     : g4_unit(q[i], hscr[wave] + (i * 8 + r) * G4_HX, ul + i, u, A); // (lanes u >= 4: .w is not a product, their acc_m is never read)
                 __builtin_amdgcn_sched_barrier(0); // one unit at a time: interleaving them costs registers, hides nothing
             }
-        };
-        auto advance = [&](int &tl, int &un) {
-            tl += step_t; un += step_u;
-            if (un >= tot) { un -= tot; tl++; }
         };
         // Staged issue: with a prologue (PRO != 0) only chunk 0 goes out before it and chunk 1 follows behind the quantizer.  The CU's vector-memory
         // queue is served in order at 64 B per clock and a wave whose requests do not fit stalls IN the issue: with both chunks (16 KiB + headers per
@@ -239,7 +235,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
             for (int d = 0; d < DC; d++) {
                 produce(q[d], h[d], tS[d], uS[d], (it * DC + d) & 1);
                 mark(); // 3, 6, ...: chunk produced
-                advance(tS[d], uS[d]);
+                ch_slot_advance(tS[d], uS[d], step_t, step_u, tot);
                 issue(q[d], h[d], tS[d], uS[d]);
                 mark(); // 4, 7, ...: next loads issued
                 __syncthreads();
@@ -264,6 +260,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
             for (int tl0 = 0; tl0 < nt; tl0 += 8) { // lane (r, u): row r of local task tl0 + u
                 const int tl = tl0 + u;
                 if (tl >= nt) continue;
+                // (text here and in the other two chain waves: as one function over the parameter struct the matrix fields come through global loads, not s_load; with only ch_mat_select the per-lane compares and selects change)
                 int wi = 0, grp = t0 + tl;
                 if (p.n_w > 1 && grp >= p.w[0].n_groups) { grp -= p.w[0].n_groups; wi = 1; }
                 if (p.n_w > 2 && wi == 1 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; wi = 2; }
@@ -293,11 +290,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
         int tl = 0, un = 0; // local task, units of it already chained
         auto row_done = [&]() {
             const float y = row_reduce<WT>(acc0, acc1, accm);
-            int wi = 0, grp = t0 + tl;
-            if (EPI != 1) {
-                if (p.n_w > 1 && grp >= p.w[0].n_groups) { grp -= p.w[0].n_groups; wi = 1; }
-                if (p.n_w > 2 && wi == 1 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; wi = 2; }
-            }
+            const auto [wi, grp] = EPI != 1 ? ch_mat_select(t0 + tl, p.n_w, p.w[0].n_groups, p.w[1].n_groups) : ChSel{0, t0 + tl};
             int64_t Nw = p.w[0].N;
             float *o = p.w[0].out;
             const float *b = p.w[0].bias;
@@ -309,29 +302,13 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
                 float v = y;
                 if (b && row < Nw) v = __fadd_rn(v, ec);
                 const float vp = dpp_f<0x128>(v); // partner row (row_ror:8 swaps the two row groups of 8 lanes)
-                const psk_rope_kv &R = p.rope;
                 const int role = wi + p.rope_wi0; // 0 q, 1 k, 2 v
-                if (u == 0 && row < Nw) {
-                    if (role == 2) {
-                        R.v_cache[row * R.n_ctx + kv_pos] = v;
-                        if (R.v16) R.v16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)v;
-                    } else {
-                        const int e = (int)(row % R.head_size);
-                        float res = v;
-                        if (e < R.n_dims) {
-                            res = ch_rope(v, vp, e, ea, eb);
-                        }
-                        if (role == 0) o[row] = res; else { R.k_cache[(int64_t)kv_pos * R.kv_dim + row] = res; if (R.k16) R.k16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)res; }
-                    }
-                }
+                if (u == 0 && row < Nw) ch_rope_kv_store(p.rope, role, o, row, kv_pos, v, vp, ea, eb);
             } else if (u == 0 && row < Nw) {
                 if (EPI == 1) {
                     ps_out_wt(o + row, g4_silu_mul(ygate, y, exp_tab));
                 } else {
-                    float v = y;
-                    if (b) v = __fadd_rn(v, ec);
-                    if (p.residual && wi == 0) v = __fadd_rn(ea, v);
-                    ps_out_wt(o + row, v);
+                    ps_out_wt(o + row, ch_bias_residual(y, b != nullptr, ec, p.residual && wi == 0, ea));
                 }
             }
             acc0 = 0.f; acc1 = 0.f; accm = 0.f;
@@ -380,10 +357,8 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemv4_kernel(const G4Params p) 
 template <int NW, int DC, int TPW, int XW, int EPI, int PRO, int YS = 0>
 void launch_g4(hipStream_t st, int grid, const G4Params &p) {
     const size_t smem = (size_t)p.col_bytes + (size_t)2 * NW * 4 * 64 * sizeof(float4) + (size_t)3 * (p.split_q + 1) * 8 * sizeof(float);
-    ps_lds_opt_in<gemv4_kernel<NW, DC, TPW, XW, EPI, PRO, YS>>(128 * 1024);
-    if (YS) psk_note_kernel("gemv4_kernel<%d, %d, %d, %d, %d, %d, %d>", NW, DC, TPW, XW, EPI, PRO, YS);
-    else psk_note_kernel("gemv4_kernel<%d, %d, %d, %d, %d, %d>", NW, DC, TPW, XW, EPI, PRO);
-    hipLaunchKernelGGL((gemv4_kernel<NW, DC, TPW, XW, EPI, PRO, YS>), dim3((unsigned)grid), dim3((NW + 1) * 64), smem, st, p);
+    ps_run<gemv4_kernel<NW, DC, TPW, XW, EPI, PRO, YS>>(st, dim3((unsigned)grid), (NW + 1) * 64, smem, 128 * 1024, p, // (the name carries YS only where it is set)
+                                                         YS ? "gemv4_kernel<%d, %d, %d, %d, %d, %d, %d>" : "gemv4_kernel<%d, %d, %d, %d, %d, %d>", NW, DC, TPW, XW, EPI, PRO, YS);
 }
 
 // KC: row-length class (tiles of 256 per row <= 16 << KC)
@@ -426,15 +401,11 @@ int psk_gemv4(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int6
         p.w[i] = G4Mat{a.w[i]->qs, a.w[i]->aux, a.out[i], a.bias[i], a.w[i]->N, ng};
         groups_total += ng;
     }
-    const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0);
-    if (epi == 2) { p.rope = *a.rope; p.rope_wi0 = a.rope_wi0; }
-    p.n_w = a.n_w; p.n_units = (int)(K / 256); p.K = (int)K;
-    p.n_tasks = epi == 1 ? p.w[0].n_groups : groups_total;
-    p.residual = a.residual; p.x = a.pro_x; p.nw = a.pro_norm_w; p.eps = a.pro_eps;
-    p.aq = act.qs; p.ad = act.d; p.abs16 = act.bs16;
+    const ChPlan pl = ch_fill(p, a, act, K, 256, a.silu_pair ? p.w[0].n_groups : groups_total, n_cu);
+    const int epi = pl.epi, grid = pl.grid;
+    if (epi == 2) p.rope_wi0 = a.rope_wi0;
+    p.abs16 = act.bs16;
     p.col_bytes = (int)psk_gemv_lds_col_bytes(PS_Q4_K, K);
-    const int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
-    p.split_q = p.n_tasks / grid; p.split_r = p.n_tasks % grid;
     p.dbg = psk_gemv_dbg_buf(epi, (epi == 0 && a.pro == 2 && K <= a.w[0]->N) ? 3 : a.pro); // timeline keys: 9 QKV, 3 O (K <= N), 5 gate/up, 2 down
     // wave configuration (measured in rounds 2-4, profiles/r04_gemv_variants.txt): rows of a multiple of 7 units take 7 producers
     const bool seven = p.n_units % 7 == 0;

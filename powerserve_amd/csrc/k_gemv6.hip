@@ -12,8 +12,7 @@
 // lane computes its sumi with v_dot4; the chain is then walked in super-block order with two lane broadcasts per step
 // (all 64 lanes redundantly carry acc[u] of their own u, so no second exchange is needed before the lane reduction).
 // HBM-bound: 210 B per 256 weights, no reuse; activations (K bytes per column) stay in L1/L2.
-#include "ps_dev.h"
-#include "ps_internal.h"
+#include "ps_gemv_dev.h"
 
 namespace {
 
@@ -105,10 +104,7 @@ __global__ __launch_bounds__(256) void gemv6_kernel(Gemv6Params p) {
         }
 #pragma unroll
         for (int c = 0; c < BS; c++) { // hsum_float_8 (ggml-quants.c:62-68): (a4+a0, a5+a1, a6+a2, a7+a3) -> (r0+r2, r1+r3) -> sum
-            float v = acc[c];
-            v = __fadd_rn(v, dpp_f<0x104>(v)); // one-directional row shifts: lane 0 of each 8-group ends with the reference's sum
-            v = __fadd_rn(v, dpp_f<0x102>(v));
-            v = __fadd_rn(v, dpp_f<0x101>(v));
+            float v = ch_hsum8(acc[c]); // (lane 0 of each 8-group ends with the reference's sum)
             if (lane == 0 && c < p.nc) {
                 if (p.bias) v = __fadd_rn(v, p.bias[row]);
                 if (p.residual) v = __fadd_rn(p.residual[(int64_t)c * p.ldo + row], v);
@@ -149,7 +145,7 @@ __global__ __launch_bounds__(256) void gemv5_kernel(Gemv5Params p) {
     const int sbl = lane >> 3, u = lane & 7;
     const int nsb = p.nsb, nit = (nsb + 7) >> 3;
     for (int64_t grow = (int64_t)blockIdx.x * 4 + wave; grow < p.N; grow += (int64_t)gridDim.x * 4) {
-        int64_t row = grow; // the wave's matrix and its row in it
+        int64_t row = grow; // the wave's matrix and its row in it (ch_mat_select's walk in rows and 64 bits: text, all four instances changed through the function)
         int wi = 0;
         if (p.n_w > 1 && row >= p.w[0].N) { row -= p.w[0].N; wi = 1; }
         if (p.n_w > 2 && wi == 1 && row >= p.w[1].N) { row -= p.w[1].N; wi = 2; }
@@ -205,10 +201,7 @@ __global__ __launch_bounds__(256) void gemv5_kernel(Gemv5Params p) {
         }
 #pragma unroll
         for (int c = 0; c < BS; c++) { // hsum_float_8 (ggml-quants.c:62-68), then + summs
-            float v = acc[c];
-            v = __fadd_rn(v, dpp_f<0x104>(v));
-            v = __fadd_rn(v, dpp_f<0x102>(v));
-            v = __fadd_rn(v, dpp_f<0x101>(v));
+            float v = ch_hsum8(acc[c]);
             v = __fadd_rn(v, summs[c]);
             if (lane == 0 && c < p.nc) {
                 if (W.bias) v = __fadd_rn(v, W.bias[row]);
@@ -217,6 +210,15 @@ __global__ __launch_bounds__(256) void gemv5_kernel(Gemv5Params p) {
             }
         }
     }
+}
+
+// f(std::integral_constant<int, BS>) with BS the column accumulators of the instance that takes nc <= 8 live columns: 1, 2, 4 or 8
+template <class F>
+void with_cols(const int nc, F &&f) {
+    if (nc == 1) f(std::integral_constant<int, 1>{});
+    else if (nc == 2) f(std::integral_constant<int, 2>{});
+    else if (nc <= 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
 }
 
 } // namespace
@@ -237,10 +239,7 @@ int psk_gemv6(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int6
         const int nc = (int)(bs - c0 < 8 ? bs - c0 : 8);
         p.aq = act.qs + c0 * K; p.ad = act.d + c0 * (K / 256);
         p.out = a.out[0] + c0 * p.ldo; p.residual = a.residual ? a.residual + c0 * p.ldo : nullptr; p.nc = nc;
-        if (nc == 1) { psk_note_kernel("gemv6_kernel<1>"); hipLaunchKernelGGL(gemv6_kernel<1>, dim3(grid), dim3(256), 0, st, p); }
-        else if (nc == 2) { psk_note_kernel("gemv6_kernel<2>"); hipLaunchKernelGGL(gemv6_kernel<2>, dim3(grid), dim3(256), 0, st, p); }
-        else if (nc <= 4) { psk_note_kernel("gemv6_kernel<4>"); hipLaunchKernelGGL(gemv6_kernel<4>, dim3(grid), dim3(256), 0, st, p); }
-        else { psk_note_kernel("gemv6_kernel<8>"); hipLaunchKernelGGL(gemv6_kernel<8>, dim3(grid), dim3(256), 0, st, p); }
+        with_cols(nc, [&](auto bsc) { ps_run<gemv6_kernel<bsc.value>>(st, dim3(grid), 256, 0, 0, p, "gemv6_kernel<%d>", bsc.value); });
     }
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -268,10 +267,7 @@ int psk_gemv5(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int6
                               (i == 0 && a.residual) ? a.residual + c0 * a.ldo[0] : nullptr};
         }
         p.nc = nc;
-        if (nc == 1) { psk_note_kernel("gemv5_kernel<1>"); hipLaunchKernelGGL(gemv5_kernel<1>, dim3(grid), dim3(256), 0, st, p); }
-        else if (nc == 2) { psk_note_kernel("gemv5_kernel<2>"); hipLaunchKernelGGL(gemv5_kernel<2>, dim3(grid), dim3(256), 0, st, p); }
-        else if (nc <= 4) { psk_note_kernel("gemv5_kernel<4>"); hipLaunchKernelGGL(gemv5_kernel<4>, dim3(grid), dim3(256), 0, st, p); }
-        else { psk_note_kernel("gemv5_kernel<8>"); hipLaunchKernelGGL(gemv5_kernel<8>, dim3(grid), dim3(256), 0, st, p); }
+        with_cols(nc, [&](auto bsc) { ps_run<gemv5_kernel<bsc.value>>(st, dim3(grid), 256, 0, 0, p, "gemv5_kernel<%d>", bsc.value); });
     }
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }

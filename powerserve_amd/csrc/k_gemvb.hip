@@ -97,17 +97,12 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvb_kernel(const GBParams p) 
         float4 xv[TPW], wv[TPW];
         if (PRO != 0) ps_qrow_load<(PRO == 1 ? 1 : 0), TPW>(p.x, p.nw, K, xv, wv, NW);
         // every unit of the ring has its own place (local task, unit inside the task) in the stream; a trip moves it DC chunks on
-        int step_t = 0, step_u = DC * UPB;
-        while (step_u >= tot) { step_u -= tot; step_t++; }
-        int tS[DC][UPW], uS[DC][UPW];
+        int step_t, step_u, tS[DC][UPW], uS[DC][UPW];
+        ch_slot_init(step_t, step_u, DC * UPB, tot);
 #pragma unroll
         for (int d = 0; d < DC; d++)
 #pragma unroll
-            for (int i = 0; i < UPW; i++) {
-                int t = 0, un = d * UPB + wave * UPW + i;
-                while (un >= tot) { un -= tot; t++; }
-                tS[d][i] = t; uS[d][i] = un;
-            }
+            for (int i = 0; i < UPW; i++) ch_slot_init(tS[d][i], uS[d][i], d * UPB + wave * UPW + i, tot);
         ps_u32x4 q[DC][UPW];
         ps_u32x2 h[DC][UPW];
         const uint32_t lane16 = (uint32_t)lane * 16u, raux = (uint32_t)r * 8u;
@@ -121,7 +116,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvb_kernel(const GBParams p) 
                 const uint8_t *qb = p.w[0].qs, *ab = p.w[0].aux;
                 if (EPI == 1) {
                     if (ul >= n_units) { ul -= n_units; qb = p.w[1].qs; ab = p.w[1].aux; }
-                } else if (p.n_w > 1 && grp >= p.w[0].n_groups) {
+                } else if (p.n_w > 1 && grp >= p.w[0].n_groups) { // (text: see k_gemv4.hip's issue)
                     grp -= p.w[0].n_groups; qb = p.w[1].qs; ab = p.w[1].aux;
                     if (p.n_w > 2 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; qb = p.w[2].qs; ab = p.w[2].aux; }
                 }
@@ -165,10 +160,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvb_kernel(const GBParams p) 
         };
         auto advance = [&](const int d) {
 #pragma unroll
-            for (int i = 0; i < UPW; i++) {
-                tS[d][i] += step_t; uS[d][i] += step_u;
-                if (uS[d][i] >= tot) { uS[d][i] -= tot; tS[d][i]++; }
-            }
+            for (int i = 0; i < UPW; i++) ch_slot_advance(tS[d][i], uS[d][i], step_t, step_u, tot);
         };
         // the CU's vector-memory queue is served in order: the activation row first, two chunks (32 KiB per CU) behind it, the
         // other two once the quantizer has run (a wave whose requests do not fit stalls IN the issue, on the prologue's path)
@@ -240,6 +232,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvb_kernel(const GBParams p) 
             for (int tl0 = 0; tl0 < nt; tl0 += TP) {
                 const int tl = tl0 + lane / RG;
                 if (tl >= nt) continue;
+                // (text here and in the other two chain waves: as one function over the parameter struct the matrix fields come through global loads, not s_load; with only ch_mat_select the per-lane compares and selects change)
                 int wi = 0, grp = t0 + tl;
                 if (p.n_w > 1 && grp >= p.w[0].n_groups) { grp -= p.w[0].n_groups; wi = 1; }
                 if (p.n_w > 2 && wi == 1 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; wi = 2; }
@@ -268,11 +261,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvb_kernel(const GBParams p) 
         int tl = 0, un = 0; // local task, units of it already chained
         auto row_done = [&]() {
             const float y = row_reduce<WT>(acc0, acc1, 0.f);
-            int wi = 0, grp = t0 + tl;
-            if (EPI != 1) {
-                if (p.n_w > 1 && grp >= p.w[0].n_groups) { grp -= p.w[0].n_groups; wi = 1; }
-                if (p.n_w > 2 && wi == 1 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; wi = 2; }
-            }
+            const auto [wi, grp] = EPI != 1 ? ch_mat_select(t0 + tl, p.n_w, p.w[0].n_groups, p.w[1].n_groups) : ChSel{0, t0 + tl};
             int64_t Nw = p.w[0].N;
             float *o = p.w[0].out;
             const float *b = p.w[0].bias;
@@ -284,28 +273,12 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvb_kernel(const GBParams p) 
                 float v = y;
                 if (b && row < Nw) v = __fadd_rn(v, ec);
                 const float vp = (LPR == 8) ? dpp_f<0x128>(v) : __shfl_xor(v, LPR, 64); // partner row
-                const psk_rope_kv &R = p.rope;
-                if (u == 0 && row < Nw) {
-                    if (wi == 2) {
-                        R.v_cache[row * R.n_ctx + kv_pos] = v;
-                        if (R.v16) R.v16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)v;
-                    } else {
-                        const int e = (int)(row % R.head_size);
-                        float res = v;
-                        if (e < R.n_dims) {
-                            res = ch_rope(v, vp, e, ea, eb);
-                        }
-                        if (wi == 0) o[row] = res; else { R.k_cache[(int64_t)kv_pos * R.kv_dim + row] = res; if (R.k16) R.k16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)res; }
-                    }
-                }
+                if (u == 0 && row < Nw) ch_rope_kv_store(p.rope, wi, o, row, kv_pos, v, vp, ea, eb);
             } else if (u == 0 && row < Nw) {
                 if (EPI == 1) {
                     ps_out_wt(o + row, g4_silu_mul(ygate, y, exp_tab));
                 } else {
-                    float v = y;
-                    if (b) v = __fadd_rn(v, ec);
-                    if (p.residual && wi == 0) v = __fadd_rn(ea, v);
-                    ps_out_wt(o + row, v);
+                    ps_out_wt(o + row, ch_bias_residual(y, b != nullptr, ec, p.residual && wi == 0, ea));
                 }
             }
             acc0 = 0.f; acc1 = 0.f;
@@ -364,9 +337,7 @@ template <int WT, int NW, int TPW, int EPI, int PRO>
 void launch_gb(hipStream_t st, int grid, const GBParams &p) {
     constexpr int UPB = NW * 2, RECF = GBT<WT>::RECF, RG = GBT<WT>::RG;
     const size_t smem = (size_t)p.act_bytes + (size_t)2 * UPB * RECF * 64 * sizeof(float4) + (size_t)3 * (p.split_q + 1) * RG * sizeof(float);
-    ps_lds_opt_in<gemvb_kernel<WT, NW, TPW, EPI, PRO>>(156 * 1024);
-    psk_note_kernel("gemvb_kernel<%d, %d, %d, %d, %d>", WT, NW, TPW, EPI, PRO);
-    hipLaunchKernelGGL((gemvb_kernel<WT, NW, TPW, EPI, PRO>), dim3((unsigned)grid), dim3((NW + 1) * 64), smem, st, p);
+    ps_run<gemvb_kernel<WT, NW, TPW, EPI, PRO>>(st, dim3((unsigned)grid), (NW + 1) * 64, smem, 156 * 1024, p, "gemvb_kernel<%d, %d, %d, %d, %d>", WT, NW, TPW, EPI, PRO);
 }
 
 template <int WT, int TPW>
@@ -407,11 +378,12 @@ bool psk_gemvb_takes(const psk_gemv_args &a, int64_t K, int64_t bs, int n_cu) {
     if ((wt != PS_Q4_0 && wt != PS_Q8_0) || K < 128 || K % 128 || K > 16384) return false;
     for (int i = 0; i < a.n_w; i++)
         if (a.w[i]->dtype != wt || a.w[i]->K != K) return false;
-    const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0), rg = wt == PS_Q4_0 ? 16 : 8, n_tasks = gb_tasks(a);
+    const int rg = wt == PS_Q4_0 ? 16 : 8, n_tasks = gb_tasks(a);
+    if (n_tasks < 1) return false;
+    const ChPlan pl = ch_plan(a, n_tasks, n_cu);
+    const int epi = pl.epi, split_q = pl.split_q, tot = (epi == 1 ? 2 : 1) * (int)(K / 128);
     if (epi == 1 && (a.n_w != 2 || a.w[0]->N != a.w[1]->N || a.pro != 1)) return false;
     if (epi == 2 && (a.n_w != 3 || a.rope_wi0 != 0 || a.pro != 1)) return false;
-    if (n_tasks < 1) return false;
-    const int split_q = n_tasks / (n_tasks < n_cu ? n_tasks : n_cu), tot = (epi == 1 ? 2 : 1) * (int)(K / 128);
     if (epi != 2 && tot <= 8) return false;
     if (epi == 0 && a.n_w == 1 && split_q >= 8 && tot <= 64) return false;
     const size_t smem = (size_t)((K + K / 8 + 15) / 16 * 16) + (size_t)2 * 16 * 3 * 64 * 16 + (size_t)3 * (split_q + 1) * rg * 4;
@@ -419,16 +391,10 @@ bool psk_gemvb_takes(const psk_gemv_args &a, int64_t K, int64_t bs, int n_cu) {
 }
 
 int psk_gemvb(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int64_t K) {
-    const int wt = a.w[0]->dtype;
-    const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0), rg = wt == PS_Q4_0 ? 16 : 8;
+    const int wt = a.w[0]->dtype, rg = wt == PS_Q4_0 ? 16 : 8;
     GBParams p{};
     for (int i = 0; i < a.n_w; i++) p.w[i] = GBMat{a.w[i]->qs, a.w[i]->aux, a.out[i], a.bias[i], a.w[i]->N, (int)((a.w[i]->N + rg - 1) / rg)};
-    if (epi == 2) p.rope = *a.rope;
-    p.n_w = a.n_w; p.n_units = (int)(K / 128); p.K = (int)K; p.n_tasks = gb_tasks(a);
-    p.residual = a.residual; p.x = a.pro_x; p.nw = a.pro_norm_w; p.eps = a.pro_eps;
-    p.aq = act.qs; p.ad = act.d;
+    const ChPlan pl = ch_fill(p, a, act, K, 128, gb_tasks(a), n_cu);
     p.act_bytes = (int)((K + K / 8 + 15) / 16 * 16);
-    const int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
-    p.split_q = p.n_tasks / grid; p.split_r = p.n_tasks % grid;
-    return wt == PS_Q4_0 ? launch_gb_wt<PS_Q4_0>(st, grid, p, epi, a.pro) : launch_gb_wt<PS_Q8_0>(st, grid, p, epi, a.pro);
+    return wt == PS_Q4_0 ? launch_gb_wt<PS_Q4_0>(st, pl.grid, p, pl.epi, a.pro) : launch_gb_wt<PS_Q8_0>(st, pl.grid, p, pl.epi, a.pro);
 }

@@ -95,17 +95,12 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
                 if (PRO == 1) { wv[i][0] = *(const float4 *)(p.nw + e); wv[i][1] = *(const float4 *)(p.nw + e + 4); }
             }
         }
-        int step_t = 0, step_u = DC * UPB; // a trip moves a unit of the ring DC chunks on
-        while (step_u >= tot) { step_u -= tot; step_t++; }
-        int tS[DC][UPW], uS[DC][UPW];
+        int step_t, step_u, tS[DC][UPW], uS[DC][UPW]; // a trip moves a unit of the ring DC chunks on
+        ch_slot_init(step_t, step_u, DC * UPB, tot);
 #pragma unroll
         for (int d = 0; d < DC; d++)
 #pragma unroll
-            for (int i = 0; i < UPW; i++) {
-                int t = 0, un = d * UPB + wave * UPW + i;
-                while (un >= tot) { un -= tot; t++; }
-                tS[d][i] = t; uS[d][i] = un;
-            }
+            for (int i = 0; i < UPW; i++) ch_slot_init(tS[d][i], uS[d][i], d * UPB + wave * UPW + i, tot);
         GKUnit<WT> ring[DC][UPW];
         // loads are UNCONDITIONAL (a unit past the range re-reads the workgroup's first unit) so that the compiler counts vmcnt
         // exactly and a chunk is consumed while the next ones are in flight
@@ -116,7 +111,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
                 int grp = t0 + (live ? tS[d][i] : 0), ul = live ? uS[d][i] : 0, wi = 0;
                 if (EPI == 1) {
                     if (ul >= n_units) { ul -= n_units; wi = 1; }
-                } else if (MULTI && p.n_w > 1 && grp >= p.w[0].n_groups) {
+                } else if (MULTI && p.n_w > 1 && grp >= p.w[0].n_groups) { // (text: through ch_mat_select every Q5_K instance trades its scalar branches for s_cselect, 119 -> 163)
                     grp -= p.w[0].n_groups; wi = 1;
                     if (p.n_w > 2 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; wi = 2; }
                 }
@@ -208,10 +203,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
         };
         auto advance = [&](const int d) {
 #pragma unroll
-            for (int i = 0; i < UPW; i++) {
-                tS[d][i] += step_t; uS[d][i] += step_u;
-                if (uS[d][i] >= tot) { uS[d][i] -= tot; tS[d][i]++; }
-            }
+            for (int i = 0; i < UPW; i++) ch_slot_advance(tS[d][i], uS[d][i], step_t, step_u, tot);
         };
         constexpr int EARLY = PRO == 0 ? DC : EA;
 #pragma unroll
@@ -284,6 +276,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
             for (int tl0 = 0; tl0 < nt; tl0 += 8) { // lane (r, u): row r of local task tl0 + u
                 const int tl = tl0 + u;
                 if (tl >= nt) continue;
+                // (text here and in the other two chain waves: as one function over the parameter struct the matrix fields come through global loads, not s_load; with only ch_mat_select the per-lane compares and selects change)
                 int wi = 0, grp = t0 + tl;
                 if (MULTI && p.n_w > 1 && grp >= p.w[0].n_groups) { grp -= p.w[0].n_groups; wi = 1; }
                 if (p.n_w > 2 && wi == 1 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; wi = 2; }
@@ -308,20 +301,14 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
         float acc = 0.f, summs = 0.f, ygate = 0.f;
         int tl = 0, un = 0; // local task, units of it already chained
         auto reduce = [&]() { // hsum_float_8 (ggml-quants.c:62-68) [+ summs]; valid in the lane with u == 0
-            float v = __fadd_rn(acc, dpp_f<0x104>(acc));
-            v = __fadd_rn(v, dpp_f<0x102>(v));
-            v = __fadd_rn(v, dpp_f<0x101>(v));
+            float v = ch_hsum8(acc);
             if (WT == PS_Q5_K) v = __fadd_rn(v, summs);
             acc = 0.f; summs = 0.f;
             return v;
         };
         auto row_done = [&]() {
             const float y = reduce();
-            int wi = 0, grp = t0 + tl;
-            if (EPI != 1) {
-                if (MULTI && p.n_w > 1 && grp >= p.w[0].n_groups) { grp -= p.w[0].n_groups; wi = 1; }
-                if (p.n_w > 2 && wi == 1 && grp >= p.w[1].n_groups) { grp -= p.w[1].n_groups; wi = 2; }
-            }
+            const auto [wi, grp] = EPI != 1 ? ch_mat_select<MULTI>(t0 + tl, p.n_w, p.w[0].n_groups, p.w[1].n_groups) : ChSel{0, t0 + tl};
             float *o = p.w[0].out;
             const float *b = p.w[0].bias;
             if (wi == 1) { o = p.w[1].out; b = p.w[1].bias; }
@@ -332,29 +319,13 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
                 float v = y;
                 if (b) v = __fadd_rn(v, ec);
                 const float vp = dpp_f<0x128>(v); // partner row (row_ror:8 swaps the two row groups of 8 lanes)
-                const psk_rope_kv &R = p.rope;
                 const int role = wi + p.rope_wi0; // 0 q, 1 k, 2 v
-                if (u == 0) {
-                    if (role == 2) {
-                        R.v_cache[row * R.n_ctx + kv_pos] = v;
-                        if (R.v16) R.v16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)v;
-                    } else {
-                        const int e = (int)(row % R.head_size);
-                        float res = v;
-                        if (e < R.n_dims) {
-                            res = ch_rope(v, vp, e, ea, eb);
-                        }
-                        if (role == 0) o[row] = res; else { R.k_cache[(int64_t)kv_pos * R.kv_dim + row] = res; if (R.k16) R.k16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)res; }
-                    }
-                }
+                if (u == 0) ch_rope_kv_store(p.rope, role, o, row, kv_pos, v, vp, ea, eb);
             } else if (u == 0) {
                 if (EPI == 1) {
                     ps_out_wt(o + row, g4_silu_mul(ygate, y, exp_tab));
                 } else {
-                    float v = y;
-                    if (b) v = __fadd_rn(v, ec);
-                    if (p.residual && wi == 0) v = __fadd_rn(ea, v);
-                    ps_out_wt(o + row, v);
+                    ps_out_wt(o + row, ch_bias_residual(y, b != nullptr, ec, p.residual && wi == 0, ea));
                 }
             }
             un = 0;
@@ -397,9 +368,8 @@ __global__ __launch_bounds__((NW + 1) * 64) void gemvk_kernel(const GKParams p) 
 template <int WT, int NW, int UPW, int DC, int EA, int TPW, int EPI, int PRO>
 void launch_gk(hipStream_t st, int grid, const GKParams &p) {
     const size_t smem = (size_t)p.act_bytes + (size_t)2 * NW * UPW * 64 * sizeof(typename GKRec<WT>::T) + (size_t)3 * (p.split_q + 1) * 8 * sizeof(float);
-    ps_lds_opt_in<gemvk_kernel<WT, NW, UPW, DC, EA, TPW, EPI, PRO>>(128 * 1024);
-    psk_note_kernel("gemvk_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", WT, NW, UPW, DC, EA, TPW, EPI, PRO);
-    hipLaunchKernelGGL((gemvk_kernel<WT, NW, UPW, DC, EA, TPW, EPI, PRO>), dim3((unsigned)grid), dim3((NW + 1) * 64), smem, st, p);
+    ps_run<gemvk_kernel<WT, NW, UPW, DC, EA, TPW, EPI, PRO>>(st, dim3((unsigned)grid), (NW + 1) * 64, smem, 128 * 1024, p, "gemvk_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", WT, NW,
+                                                              UPW, DC, EA, TPW, EPI, PRO);
 }
 
 template <int WT, int UPW, int DC, int EA, int TPW>
@@ -448,14 +418,9 @@ int psk_gemvk(hipStream_t st, int n_cu, const psk_gemv_args &a, ps_act act, int6
         p.w[i] = GKMat{w->qs, w->qh, w->sc, (const uint16_t *)w->aux, a.out[i], a.bias[i], w->N, ng};
         groups_total += ng;
     }
-    const int epi = a.silu_pair ? 1 : (a.rope ? 2 : 0);
-    if (epi == 2) { p.rope = *a.rope; p.rope_wi0 = a.rope_wi0; }
-    p.n_w = a.n_w; p.n_units = (int)(K / 256); p.K = (int)K;
-    p.n_tasks = epi == 1 ? p.w[0].n_groups : groups_total;
-    p.residual = a.residual; p.x = a.pro_x; p.nw = a.pro_norm_w; p.eps = a.pro_eps;
-    p.aq = act.qs; p.ad = act.d; p.abs16 = act.bs16;
+    const ChPlan pl = ch_fill(p, a, act, K, 256, a.silu_pair ? p.w[0].n_groups : groups_total, n_cu);
+    if (pl.epi == 2) p.rope_wi0 = a.rope_wi0;
+    p.abs16 = act.bs16;
     p.act_bytes = (int)((K + (K / 256) * 4 + (K / 32) * 4 + 15) / 16 * 16);
-    const int grid = p.n_tasks < n_cu ? p.n_tasks : n_cu;
-    p.split_q = p.n_tasks / grid; p.split_r = p.n_tasks % grid;
-    return wt == PS_Q6_K ? launch_gk_wt<PS_Q6_K>(st, grid, p, epi, a.pro) : launch_gk_wt<PS_Q5_K>(st, grid, p, epi, a.pro);
+    return wt == PS_Q6_K ? launch_gk_wt<PS_Q6_K>(st, pl.grid, p, pl.epi, a.pro) : launch_gk_wt<PS_Q5_K>(st, pl.grid, p, pl.epi, a.pro);
 }

@@ -1,5 +1,6 @@
-// Device code shared by the quantized mat-vec kernels (k_gemv.hip: gemv / gemv1 / gemm8*, k_gemv4.hip, k_gemvb.hip, k_gemvk.hip):
-// weight-type traits, the LDS image of an activation column, the per-unit integer work (unit_dot) and hsum_float_8 (row_reduce).  See k_gemv.hip's header for the numerics contract.
+// Device code shared by the quantized mat-vec kernels (k_gemv.hip: gemv / gemv1 / gemm8*, k_gemv4.hip, k_gemvb.hip, k_gemvk.hip, k_gemv6.hip):
+// weight-type traits, the LDS image of an activation column, the per-unit integer work (unit_dot), hsum_float_8 (ch_hsum8 -- k_gemv6.hip takes it too -- and row_reduce), the chain wave's
+// matrix select, slot and epilogue arithmetic, and the host side of a producer / chain-wave launch (ch_plan, ch_fill).  See k_gemv.hip's header for the numerics contract.
 #pragma once
 // (round 6) what a decode step STREAMS and reads once per token should not cycle through the L2s and the memory-side cache in front of what is reused (activations,
 // exchanges): the quants carry the non-temporal hint since round 2; the cached K rows / V channels since round 6 (k_qkvattn.hip KVS, k_attn.hip: +2.1 % decode on the 8B shape).
@@ -94,20 +95,24 @@ __device__ __forceinline__ void unit_dot(const uint4 q, const uint4 h, const int
     }
 }
 
+// hsum_float_8 (ggml-quants.c:62-68) over the eight lanes of a row: (a4+a0, a5+a1, a6+a2, a7+a3) -> (r0+r2, r1+r3) -> sum, valid in the lane with u == 0.
+// One-directional DPP row shifts (lane u reads lane u + n inside its row of 16): the partners and the association of the xor butterfly, no ds_bpermute round trip
+__device__ __forceinline__ float ch_hsum8(const float a) {
+    float r = __fadd_rn(a, dpp_f<0x104>(a));
+    r = __fadd_rn(r, dpp_f<0x102>(r));
+    return __fadd_rn(r, dpp_f<0x101>(r));
+}
+
 // hsum_float_8 association (+ acc_m for Q4_K): valid in the lane with u == 0
 template <int WT>
 __device__ __forceinline__ float row_reduce(float acc0, float acc1, float accm) {
-    // only u == 0 keeps the result: one-directional DPP row shifts (lane u reads lane u + n inside its row of 16) give the
-    // same partners and association as the xor butterfly without any ds_bpermute round trip on the chain waves' path
-    if (WT == PS_Q4_0) {
+    if (WT == PS_Q4_0) { // (four lanes per row: the first step is the lane's own acc1 + acc0)
         float r = __fadd_rn(acc1, acc0); // a[k+4] + a[k]
         r = __fadd_rn(r, dpp_f<0x102>(r));
         r = __fadd_rn(r, dpp_f<0x101>(r));
         return r;
     }
-    float r = __fadd_rn(acc0, dpp_f<0x104>(acc0));
-    r = __fadd_rn(r, dpp_f<0x102>(r));
-    r = __fadd_rn(r, dpp_f<0x101>(r));
+    float r = ch_hsum8(acc0);
     if (WT == PS_Q4_K) {
         float m = __fadd_rn(accm, dpp_f<0x102>(accm)); // (m0+m2), (m1+m3)
         m = __fadd_rn(m, dpp_f<0x101>(m));
@@ -141,7 +146,51 @@ __device__ __forceinline__ float ch_rope(const float v, const float vp, const in
     return ps_rope_one(x0, x1, c, s, (e & 1) != 0);
 }
 
+// Up to three matrices share a launch (Q / K / V, gate / up) and its row groups are numbered through: the walk from a launch-wide group index to (matrix wi, group
+// inside it), n0 / n1 the group counts of w[0] / w[1].  MULTI = false: the launch carries one matrix (gemvk's Q6_K), nothing to walk.  The chain waves' row_done calls it,
+// where the index is wave-uniform; the sites that walk per lane or in 64 bits keep their text (they compile to other code through a function: HISTORY.md, round 18).
+struct ChSel { int wi, grp; };
+template <bool MULTI = true>
+__device__ __forceinline__ ChSel ch_mat_select(int grp, const int n_w, const int n0, const int n1) {
+    int wi = 0;
+    if (MULTI && n_w > 1 && grp >= n0) { grp -= n0; wi = 1; }
+    if (n_w > 2 && wi == 1 && grp >= n1) { grp -= n1; wi = 2; }
+    return {wi, grp};
+}
+
 // ---- shared by the producer / chain-wave kernels (k_gemv4.hip, k_gemvb.hip, k_gemvk.hip)
+// A producer's ring slot and its place in the workgroup's stream: stream unit s -> (local task t, unit u inside it) of tasks of `tot` units; a trip of the ring moves it
+// (step_t, step_u) on.  gemv4's slot is four units of one row, gemvb's and gemvk's one unit: one (t, u) pair either way.
+__device__ __forceinline__ void ch_slot_init(int &t, int &u, const int s, const int tot) {
+    t = 0; u = s;
+    while (u >= tot) { u -= tot; t++; }
+}
+__device__ __forceinline__ void ch_slot_advance(int &t, int &u, const int step_t, const int step_u, const int tot) {
+    t += step_t; u += step_u;
+    if (u >= tot) { u -= tot; t++; }
+}
+// EPI 0 of a finished row: y (+ bias) (+ residual) in the reference's operand order (mat-mul, add(y, bias), add(residual, that))
+__device__ __forceinline__ float ch_bias_residual(float v, const bool has_bias, const float bias, const bool has_res, const float res) {
+    if (has_bias) v = __fadd_rn(v, bias);
+    if (has_res) v = __fadd_rn(res, v);
+    return v;
+}
+// EPI 2 of a finished row (value v, bias added; vp its rotation partner's; (c, s) of the pair): role 0 q -> RoPE -> o, role 1 k -> RoPE -> row kv_pos of the K cache,
+// role 2 v -> column kv_pos of the transposed V cache; the fp16 mirrors where the model keeps them
+__device__ __forceinline__ void ch_rope_kv_store(const psk_rope_kv &R, const int role, float *o, const int64_t row, const int kv_pos, const float v, const float vp, const float c,
+                                                 const float s) {
+    if (role == 2) {
+        R.v_cache[row * R.n_ctx + kv_pos] = v;
+        if (R.v16) R.v16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)v;
+    } else {
+        const int e = (int)(row % R.head_size);
+        float res = v;
+        if (e < R.n_dims) {
+            res = ch_rope(v, vp, e, c, s);
+        }
+        if (role == 0) o[row] = res; else { R.k_cache[(int64_t)kv_pos * R.kv_dim + row] = res; if (R.k16) R.k16[(int64_t)kv_pos * R.kv_dim + row] = (_Float16)res; }
+    }
+}
 // silu_hadamard (src/backend/ggml/ggml.cpp:115-129) with glibc's expf table read from LDS: a table lookup in global /
 // constant memory is a vector-memory round trip (> 1 us behind the weight stream) on the chain wave's critical path
 __device__ __forceinline__ float g4_silu_mul(float g, float u, const uint64_t *tab) {
@@ -221,6 +270,26 @@ __device__ __forceinline__ void g4_quantize_pair(const float v[8], const int e0,
         d[t] = dd;
         bs32[e0 >> 5] = s;
     }
+}
+
+// ---- host side of the producer / chain-wave launches (psk_gemv4, psk_gemvb, psk_gemvk)
+// The plan: the epilogue kind of the group (0 bias / residual, 1 SiLU pair, 2 RoPE + KV append) and its n_tasks >= 1 row groups (a SiLU pair: row-group pairs) split
+// over at most n_cu persistent workgroups -- split_q each, one more for the first split_r
+struct ChPlan { int epi, grid, split_q, split_r; };
+inline ChPlan ch_plan(const psk_gemv_args &a, const int n_tasks, const int n_cu) {
+    const int grid = n_tasks < n_cu ? n_tasks : n_cu;
+    return {a.silu_pair ? 1 : (a.rope ? 2 : 0), grid, n_tasks / grid, n_tasks % grid};
+}
+// ... and the fields that G4Params, GBParams and GKParams share, filled from it (unit: elements of a stream unit per row)
+template <class P>
+inline ChPlan ch_fill(P &p, const psk_gemv_args &a, const ps_act act, const int64_t K, const int unit, const int n_tasks, const int n_cu) {
+    const ChPlan pl = ch_plan(a, n_tasks, n_cu);
+    p.n_w = a.n_w; p.n_units = (int)(K / unit); p.K = (int)K;
+    p.n_tasks = n_tasks; p.split_q = pl.split_q; p.split_r = pl.split_r;
+    p.residual = a.residual; p.x = a.pro_x; p.nw = a.pro_norm_w; p.eps = a.pro_eps;
+    p.aq = act.qs; p.ad = act.d;
+    if (pl.epi == 2) p.rope = *a.rope;
+    return pl;
 }
 
 } // namespace

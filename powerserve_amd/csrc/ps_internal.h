@@ -238,6 +238,15 @@ unsigned long long *psk_gemv_dbg_buf(int epi, int pro);
 // the template instance the last quantized mat-vec / mat-mul launch of this process used (rocprofv3's kernel name): bench.py's
 // roofline names the kernel that RAN, not the one it expects
 void psk_note_kernel(const char *fmt, ...);
+// One launch of a kernel instance: its opt-in to `opt_in` bytes of dynamic LDS (0: none here -- it never asks for more than the 64 KiB it gets unasked, or its caller has opted in), the name
+// ps_hip_last_matmul_kernel reports for it -- the instance's own format string beside its template arguments; the tests and bench.py's roofline read these strings --
+// and the launch.
+template <auto KERNEL, class P, class... A>
+static inline void ps_run(hipStream_t st, const dim3 grid, const int block, const size_t smem, const int opt_in, const P &p, const char *fmt, const A... args) {
+    if (opt_in) ps_lds_opt_in<KERNEL>(opt_in);
+    psk_note_kernel(fmt, args...);
+    hipLaunchKernelGGL(KERNEL, grid, dim3((unsigned)block), smem, st, p);
+}
 const char *psk_last_kernel();
 // the same for the single-token attention (ps_hip_last_attention_kernel): which of the fused Q / K / V + attention launch, attn_decode2, the scores + soft-max.V.p
 // pair or attn_flash16 the last single-token forward enqueued -- noted at enqueue time, so a captured graph reports what it captured

@@ -422,6 +422,65 @@ def test_chunk_matmul_forms_match_oracle(ctx, oracle, tmp_path, preset, kernels)
     gm.close()
 
 
+# (model dim, weight type) -> the last launch of a single token's launch groups as ps_hip_model_bench_matmul replays them (2 Q / K / V, 3 O, 1 gate / up, 4 down, 5 lm_head),
+# read off the parent of round 18 on 256 CUs.  Q4_0 / Q8_0 rows of 8 units (dim 1024) are gemv1's, the SiLU pair and the 16-unit down rows gemvb's.
+def _matvec_table(qkv, o, gate_up, down, lm_head):
+    return {2: qkv, 3: o, 1: gate_up, 4: down, 5: lm_head}
+
+
+MATVEC_KERNELS = {}
+for _dim in (1024, 2048):
+    MATVEC_KERNELS[(_dim, 12)] = _matvec_table("gemv4_kernel<8, 2, 2, 2, 0, 1>", "gemv4_kernel<8, 2, 2, 2, 0, 2>", "gemv4_kernel<8, 2, 2, 2, 1, 1, 1>",
+                                               "gemv4_kernel<8, 2, 2, 2, 0, 2>", "gemv4_kernel<8, 2, 2, 2, 0, 1>")
+    MATVEC_KERNELS[(_dim, 13)] = _matvec_table("gemvk_kernel<13, 8, 2, 3, 1, 2, 0, 1>", "gemvk_kernel<13, 8, 2, 3, 1, 2, 0, 2>", "gemvk_kernel<13, 8, 2, 3, 1, 2, 1, 1>",
+                                               "gemvk_kernel<13, 8, 2, 3, 1, 2, 0, 2>", "gemvk_kernel<13, 8, 2, 3, 1, 2, 0, 1>")
+    # Q6_K: a launch per matrix (Q / K / V: three, the name is V's; gate / up: two and the SiLU op behind them, the name is up's)
+    MATVEC_KERNELS[(_dim, 14)] = _matvec_table("gemvk_kernel<14, 8, 2, 3, 1, 2, 0, 1>", "gemvk_kernel<14, 8, 2, 3, 1, 2, 0, 2>", "gemvk_kernel<14, 8, 2, 3, 1, 2, 0, 1>",
+                                               "gemvk_kernel<14, 8, 2, 3, 1, 2, 0, 2>", "gemvk_kernel<14, 8, 2, 3, 1, 2, 0, 1>")
+for _wt in (2, 8):
+    MATVEC_KERNELS[(1024, _wt)] = _matvec_table(f"gemv1_kernel<{_wt}, 2, 4, 0, 1>", f"gemv1_kernel<{_wt}, 2, 4, 0, 2>", f"gemvb_kernel<{_wt}, 8, 1, 1, 1>",
+                                                f"gemvb_kernel<{_wt}, 8, 1, 0, 2>", f"gemv1_kernel<{_wt}, 2, 4, 0, 1>")
+    MATVEC_KERNELS[(2048, _wt)] = _matvec_table(f"gemvb_kernel<{_wt}, 8, 1, 0, 1>", f"gemvb_kernel<{_wt}, 8, 1, 0, 2>", f"gemvb_kernel<{_wt}, 8, 1, 1, 1>",
+                                                f"gemvb_kernel<{_wt}, 8, 2, 0, 2>", f"gemvb_kernel<{_wt}, 8, 1, 0, 1>")
+
+
+@pytest.mark.parametrize("wt", [12, 2, 8, 13, 14])
+@pytest.mark.parametrize("preset", ["small-qwen2-hs128", "wide-qwen2-hs128", "small-llama-hs128"])
+def test_decode_matvec_forms_match_oracle(ctx, oracle, tmp_path, preset, wt):
+    """Every producer / chain-wave mat-vec of a single token (k_gemv4.hip, k_gemvb.hip, k_gemvk.hip) and the Q5_K / Q6_K / fallback kernels behind them inside a
+    model: a 5-token prompt as one batch, then 4 single tokens; every single token's logits and layer 0's K rows and V columns bit-equal to the oracle.  Dims 1024
+    and 2048 with hidden sizes 2048 and 3072 (rows of 4 to 24 units), the Qwen2 presets carry the Q / K / V bias through every EPI 2 and EPI 0 copy, all three the
+    three-matrix select, the SiLU pair and the residual.  The replay of a token's launch groups then names the kernel that served each; where a group goes out
+    in more than one launch (a Q6_K Q / K / V: one launch per matrix) the name is the last launch's."""
+    import ctypes as C
+    from oracle import binding as B
+    from powerserve_amd import hip, synth
+    d = str(tmp_path / "m")
+    mj = synth.write_model_dir(d, preset, wt, n_ctx=256, seed=31 + wt)
+    cfg = B.make_config(mj["llm_config"])
+    om = oracle.model(cfg, mj["model_arch"], load_tensors(os.path.join(d, "ggml/weights.gguf")), n_threads=16)
+    toks = np.random.default_rng(29 + wt).integers(0, cfg.vocab_size, 9)
+    om.forward(toks[:5], np.arange(5), False)
+    want = [om.forward(toks[i:i + 1], [i], True) for i in range(5, 9)]
+    want_k, want_v = om.k_cache(0)[:9].copy(), om.v_cache(0)[:, :9].copy()
+    om.close()
+    gm = hip.Model(ctx, d, max_batch=16, n_ctx=256)
+    gm.forward(toks[:5], np.arange(5), lm_head=False)
+    for i, w in zip(range(5, 9), want):
+        got, _ = gm.forward(toks[i:i + 1], [i], True)
+        assert np.array_equal(got.view(np.uint32), w.view(np.uint32)), (i, rel_err(got, w))
+    assert np.array_equal(gm.k_cache(0)[:9].view(np.uint32), want_k.view(np.uint32))
+    assert np.array_equal(gm.v_cache(0)[:, :9].view(np.uint32), want_v.view(np.uint32))
+    seen = {}
+    for which in (2, 3, 1, 4, 5):
+        seq_ms, null_ms, n = C.c_double(), C.c_double(), C.c_int()
+        ctx.check(ctx.L.ps_hip_model_bench_matmul(gm.h, 1, which, 1, C.byref(seq_ms), C.byref(null_ms), C.byref(n)))
+        seen[which] = ctx.L.ps_hip_last_matmul_kernel().decode()
+    print(preset, wt, seen)
+    gm.close()
+    assert seen == MATVEC_KERNELS[(cfg.dim, wt)]
+
+
 @pytest.mark.parametrize("wt", [12, 1015, 1017])  # pure Q4_K; the Q4_K_M mix (Q6_K attn_v / ffn_down / output: the prefill chunks take gemm6k); Q5_K_M (Q5_K producer + gemm6k)
 def test_long_context_batches_match_oracle(ctx, oracle, tmp_path, wt):
     """Batches appended behind a long KV prefix (n_kv > 256: several 32-column chain rounds, leftovers, softmax tails):

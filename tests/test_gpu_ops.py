@@ -143,6 +143,27 @@ def test_mul_mat_fallback_routes(ctx, oracle, hip, wt, K, N, bs, kernel):
     W.free()
 
 
+@pytest.mark.parametrize("wt,name", [(13, "gemv5_kernel"), (14, "gemv6_kernel")])
+@pytest.mark.parametrize("K,N,bs,cols", [(256, 37, 1, 1), (256, 40, 2, 2), (256, 40, 3, 4), (256, 40, 8, 8), (256, 40, 9, 1), (256, 40, 11, 4)])
+def test_mul_mat_q5k_q6k_row_kernels(ctx, oracle, hip, wt, name, K, N, bs, cols):
+    """Every instance of the one-wave-per-row Q5_K / Q6_K kernels (k_gemv6.hip: 1, 2, 4 and 8 column accumulators), the smallest shape that reaches each:
+    one super-block per row, N = 40 rows (not a multiple of 32: the matrix-core chunk kernels decline every column count) with 2, 3 and 8 columns, 9 and 11
+    columns for the second launch of a call (8 + 1, 8 + 3: the name is the last launch's), and a single column of N = 37 rows, which k_gemvk.hip declines
+    (N % 8 != 0) and the dispatcher quantizes ahead of the launch.  Bit-equal to the oracle, the instance pinned."""
+    from powerserve_amd import synth
+    rng = np.random.default_rng(wt * 137 + K + N + bs)
+    w = synth.random_blocks(rng, wt, N, K)
+    x = (rng.standard_normal((bs, K)) * rng.uniform(0.1, 30.0, (bs, 1))).astype(np.float32)
+    want = oracle.mul_mat(wt, w, K, N, x)
+    W = ctx.upload_weight(wt, w, K, N)
+    dx, dy = ctx.to_device(x), ctx.empty((bs, N))
+    ctx.check(ctx.L.ps_hip_mul_mat(ctx.h, C.byref(dy.tensor()), C.byref(W.tensor()), C.byref(dx.tensor())))
+    assert ctx.L.ps_hip_last_matmul_kernel().decode() == f"{name}<{cols}>"
+    got = dy.numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (rel_err(got, want), np.argwhere(got != want)[:8])
+    W.free()
+
+
 def test_mul_mat_small_rows_then_rows_past_64k_of_lds(ctx, oracle, hip):
     """One instantiation, gemv_kernel<8, 4, 0, 0, 4>, first with a column image far below 64 KiB of LDS (K = 160) and then above it (K = 12320: four
     columns of 17 072 bytes = 68 288): the opt-in to more than 64 KiB belongs to the kernel, not to the size of its first launch, so the second

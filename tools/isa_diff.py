@@ -10,7 +10,7 @@ difference.  --keep DIR keeps the .s files (DIR/a, DIR/b) and reuses one when it
 import collections, importlib.util, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-FILES = ["k_gemv4.hip", "k_gemvb.hip", "k_gemvk.hip", "k_qkvattn.hip", "k_attn.hip", "k_attn_long.hip", "k_gemm4k.hip"]
+FILES = ["k_gemv4.hip", "k_gemvb.hip", "k_gemvk.hip", "k_gemv6.hip", "k_gemv.hip", "k_qkvattn.hip", "k_attn.hip", "k_attn_long.hip", "k_gemm4k.hip"]
 KEYS = [".vgpr_count", ".agpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count"]
 
 
