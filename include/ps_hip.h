@@ -273,6 +273,11 @@ typedef struct ps_sample_state {
 int ps_hip_sample_covered(const ps_sample_cfg *cfg, int n_vocab, const ps_sample_state *state);
 /* one step on caller logits (device float[n_vocab]): *token_out (host) = the drawn token, *state advanced */
 int ps_hip_sample(ps_hip_ctx *ctx, const float *logits_dev, int n_vocab, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *token_out);
+/* ps_hip_sample for `rows` rows of caller logits in one pair of launches: row r at logits_dev + r * row_stride (floats, row_stride >= n_vocab; any alignment),
+ * its own cfgs[r] / states[r]; tokens_out HOST int32[rows].  1 <= rows <= 16.  Row r draws what ps_hip_sample draws on that row alone, and states[r] advances
+ * the same way.  A row whose configuration is not covered refuses the whole call (rc 2, the message names the row, no state modified). */
+int ps_hip_sample_rows(ps_hip_ctx *ctx, const float *logits_dev, int n_vocab, int64_t row_stride, int rows,
+                       const ps_sample_cfg *cfgs, ps_sample_state *states, int32_t *tokens_out);
 /* ps_hip_model_decode_greedy with the drawn token in place of the arg-max: its own captured step (dropped where the greedy one is),
  * eager in mode bit 0, hidden slots refused, one retry from the start state after an attention time-out.  *state advanced. */
 int ps_hip_model_decode_sampled(ps_hip_model *m, int32_t token, int steps, const ps_sample_cfg *cfg, ps_sample_state *state, int32_t *out_ids);
@@ -322,6 +327,13 @@ int ps_hip_model_seq_select(ps_hip_model *m, int seq);
 int ps_hip_model_decode_batch(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int lm_head, int32_t *argmax_host);
 /* `steps` such steps, each column fed its own arg-max, without a host round trip per step.  out_ids HOST int32[steps][n]. */
 int ps_hip_model_decode_batch_greedy(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int steps, int32_t *out_ids);
+/* ps_hip_model_decode_batch_greedy with column i fed the token its own chain drew: cfgs / states are arrays of n entries (column i: cfgs[i], states[i]);
+ * out_ids HOST int32[steps][n]; states advanced.  Column i is, id for id, what ps_hip_model_decode_sampled draws on a one-sequence model with the same history,
+ * first token, cfgs[i] and start state states[i], whoever else is in the batch and whatever their configurations (DESIGN.md "Sampled batched decode").
+ * rc 2, nothing advanced and no state modified (the message names the column): what decode_batch_greedy refuses, a null pointer, a column whose configuration
+ * ps_hip_sample_covered refuses for the model's vocabulary.  steps <= 0: 0, nothing changed. */
+int ps_hip_model_decode_batch_sampled(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int steps,
+                                      const ps_sample_cfg *cfgs, ps_sample_state *states, int32_t *out_ids);
 /* Fork (DESIGN.md "Fork, save and restore").  A forward only writes slots at or behind the position, so a prefix of one sequence is, bit for bit, a valid prefix of
  * another: one prefill serves every conversation behind the same system prompt and every one of n / best_of completions.
  * dst sequences get slots [0, n_tokens) of src's K / V in every layer; their position becomes n_tokens, all their slots visible.  Afterwards each destination behaves in

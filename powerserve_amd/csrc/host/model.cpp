@@ -370,6 +370,13 @@ bool device_sampler_state(const SamplerChain &sampler, ps_sample_cfg &c, ps_samp
     return true;
 }
 
+// ... and the way back: the engine a device run left in st becomes the chain's
+static void load_engine_state(SamplerChain &sampler, const ps_sample_state &st) {
+    std::string e;
+    for (int i = 0; i < 624; i++) e += std::to_string(st.mt[i]) + ' ';
+    sampler.set_engine_state(e + std::to_string(st.mt_pos));
+}
+
 auto Model::generate(const std::vector<Token> &prompt, int steps, size_t batch_size, SamplerChain &sampler) -> std::vector<Token> {
     std::vector<Token> out;
     if (steps <= 0 || prompt.empty()) return out;
@@ -386,9 +393,7 @@ auto Model::generate(const std::vector<Token> &prompt, int steps, size_t batch_s
             POWERSERVE_ABORT(std::string("decode_sampled: ") + ps_hip_last_error(backend().m_ctx));
         backend().reset_threadpool();
         for (Token t : out) sampler.accept(t);
-        std::string e;
-        for (int i = 0; i < 624; i++) e += std::to_string(ds.mt[i]) + ' ';
-        sampler.set_engine_state(e + std::to_string(ds.mt_pos));
+        load_engine_state(sampler, ds);
         return out;
     }
     Token cur = prompt.back();
@@ -396,6 +401,42 @@ auto Model::generate(const std::vector<Token> &prompt, int steps, size_t batch_s
         auto ret = forward({cur}, {(int)m_platform->get_kv_position(id)}, CausalAttentionMask(1), true);
         cur = sampler.sample(ret.logits_vector[0]);
         out.push_back(cur);
+    }
+    return out;
+}
+
+auto Model::decode_batch_sampled(const std::vector<int> &seq_ids, const std::vector<Token> &tokens, int steps, const std::vector<SamplerChain *> &samplers)
+    -> std::vector<Token> {
+    const size_t n = tokens.size();
+    POWERSERVE_ASSERT(n == seq_ids.size() && n == samplers.size() && n > 0);
+    std::vector<Token> out;
+    if (steps <= 0) return out;
+    auto &be = backend();
+    const int vocab = (int)m_config->llm.vocab_size;
+    std::vector<ps_sample_cfg> dc(n);
+    std::vector<ps_sample_state> ds(n);
+    bool device = m_device_sampling;
+    for (size_t i = 0; device && i < n; i++)
+        device = samplers[i]->standard() && device_sampler_state(*samplers[i], dc[i], ds[i]) && ps_hip_sample_covered(&dc[i], vocab, &ds[i]) == 0;
+    std::vector<int32_t> s(seq_ids.begin(), seq_ids.end()), t(tokens.begin(), tokens.end());
+    if (device) { // every chain on the device, one library call; the chains then take their ids and their engines back, as in generate()
+        std::vector<int32_t> ids((size_t)steps * n);
+        if (ps_hip_model_decode_batch_sampled(be.m_model, s.data(), t.data(), (int)n, steps, dc.data(), ds.data(), ids.data()))
+            POWERSERVE_ABORT(std::string("decode_batch_sampled: ") + ps_hip_last_error(be.m_ctx));
+        for (size_t i = 0; i < n; i++) {
+            for (int k = 0; k < steps; k++) samplers[i]->accept(ids[(size_t)k * n + i]);
+            load_engine_state(*samplers[i], ds[i]);
+        }
+        return std::vector<Token>(ids.begin(), ids.end());
+    }
+    // the host loop, for the whole call: a batched step with the logits to the host, every row through its chain
+    std::vector<float> logits(n * (size_t)vocab);
+    for (int k = 0; k < steps; k++) {
+        decode_batch(seq_ids, std::vector<Token>(t.begin(), t.end()), logits.data());
+        for (size_t i = 0; i < n; i++) {
+            t[i] = samplers[i]->sample(std::span<const float>(logits.data() + i * (size_t)vocab, (size_t)vocab));
+            out.push_back(t[i]);
+        }
     }
     return out;
 }
@@ -475,6 +516,16 @@ int psh_model_decode_batch(void *h, const int32_t *seq_ids, const int32_t *token
         auto m = (psh_model *)h;
         auto r = m->model->decode_batch(std::vector<int>(seq_ids, seq_ids + n), std::vector<Token>(tokens, tokens + n), logits_out);
         for (int i = 0; i < n; i++) ids_out[i] = r[i];
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+int psh_model_decode_batch_sampled(void *h, const int32_t *seq_ids, const int32_t *tokens, int n, int steps, void *const *chains, int32_t *ids_out) { // Model::decode_batch_sampled: ids_out [steps][n]
+    try {
+        auto m = (psh_model *)h;
+        std::vector<SamplerChain *> ch((size_t)n);
+        for (int i = 0; i < n; i++) ch[i] = (SamplerChain *)chains[i];
+        auto r = m->model->decode_batch_sampled(std::vector<int>(seq_ids, seq_ids + n), std::vector<Token>(tokens, tokens + n), steps, ch);
+        std::copy(r.begin(), r.end(), ids_out);
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return 1; }
 }

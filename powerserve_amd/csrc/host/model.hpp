@@ -94,6 +94,11 @@ struct Model {
     // one greedy step: tokens[i] goes to sequence seq_ids[i] at that sequence's position and advances it; returns the arg-max id per column.
     // logits_out (optional): host [n][vocab] logits of the columns
     auto decode_batch(const std::vector<int> &seq_ids, const std::vector<Token> &tokens, float *logits_out = nullptr) -> std::vector<Token>;
+    // `steps` batched steps, column i fed the token samplers[i] drew from its logits; returns the ids [steps][n], row after row.  Standard chains the device covers
+    // (device_sampler_state) run on the device in one call (ps_hip_model_decode_batch_sampled) and take their ids (accept) and engines back; one chain that is
+    // not, or m_device_sampling off, and the whole call is the host loop: decode_batch with the logits to the host, sample per row.  Same ids, same chains afterwards
+    auto decode_batch_sampled(const std::vector<int> &seq_ids, const std::vector<Token> &tokens, int steps, const std::vector<SamplerChain *> &samplers)
+        -> std::vector<Token>;
     // fork: the first n_tokens slots of sequence src become the history of every sequence of dsts (ps_hip_model_seq_fork: one launch, src untouched) -- one prefill
     // of a shared system prompt, or of the prompt of n / best_of completions (app/server/openai_api.hpp:122-123), serves them all
     void fork_sequence(size_t src, const std::vector<int> &dsts, size_t n_tokens);

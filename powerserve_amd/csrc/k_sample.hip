@@ -7,6 +7,10 @@
 //                        when the k + 1 largest values are not pairwise distinct or a NaN is anywhere, std::partial_sort's
 //                        own heap mechanics over `pen` instead (the exact path); then the chain's tail and the draw
 //                        (ps_sample_dev.h) on the device-resident mt19937, and the decode bookkeeping of psl_argmax2
+// Each kernel has a second entry for the rows of a batched step (psl_sample_rows: a ps_sample_dev and a scratch of psl_sample_scratch_bytes per row), both on row
+// blockIdx.y: sample_slice_rows_kernel on a (slices, rows) grid calls sample_slice_body like sample_slice_kernel; sample_final_rows_kernel on a (1, rows) grid holds the
+// same statements as sample_final_kernel, one copy of text included into both (ps_sample_final_body.h says why it is not a function).  A row's workgroups touch that
+// row's buffers only.
 #include "ps_internal.h"
 #include "ps_ops.h"
 #include "ps_sample_dev.h"
@@ -15,6 +19,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <vector>
 
 namespace {
 
@@ -35,7 +40,9 @@ __device__ __forceinline__ float fkey_val(uint32_t k) { return __uint_as_float((
 __device__ __forceinline__ unsigned long long ckey(float v, int t) { return ((unsigned long long)~fkey(v) << 32) | (uint32_t)t; }
 __device__ __forceinline__ float ckey_val(unsigned long long k) { return fkey_val(~(uint32_t)(k >> 32)); }
 
-template <int N, int NT> __device__ void bitonic_sort_asc(unsigned long long *s) {
+// ENTRY: one instance per kernel that sorts, so that each has the single caller it always had (the compiler inlines those; with two callers it keeps a function, and
+// under __forceinline__ sample_final_kernel comes out differently: HISTORY round 19)
+template <int N, int NT, int ENTRY = 0> __device__ void bitonic_sort_asc(unsigned long long *s) {
     for (int size = 2; size <= N; size <<= 1)
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             __syncthreads();
@@ -49,7 +56,22 @@ template <int N, int NT> __device__ void bitonic_sort_asc(unsigned long long *s)
     __syncthreads();
 }
 
-__global__ __launch_bounds__(SL_NT) void sample_slice_kernel(const float *logits, int n, const ps_sample_dev *d, float *pen, unsigned long long *cand, int *flags) {
+// one row's scratch: the slices' candidate lists, the penalised row, the slices' NaN flags (psl_sample_scratch_bytes)
+struct sample_scratch {
+    unsigned long long *cand;
+    float *pen;
+    int *flags;
+};
+__host__ __device__ __forceinline__ sample_scratch sample_carve(void *scratch, int nwg, int n) {
+    sample_scratch s;
+    s.cand = (unsigned long long *)scratch;
+    s.pen = (float *)(s.cand + (size_t)nwg * (PS_SAMPLE_K_MAX + 1));
+    s.flags = (int *)(s.pen + n);
+    return s;
+}
+
+// slice blockIdx.x of one row
+template <int ENTRY> __device__ __forceinline__ void sample_slice_body(const float *logits, int n, const ps_sample_dev *d, float *pen, unsigned long long *cand, int *flags) {
     __shared__ float sv[SL];
     __shared__ unsigned long long sk[SL];
     __shared__ int snan;
@@ -81,9 +103,12 @@ __global__ __launch_bounds__(SL_NT) void sample_slice_kernel(const float *logits
         }
     }
     if (nan) snan = 1;
-    bitonic_sort_asc<SL, SL_NT>(sk);
+    bitonic_sort_asc<SL, SL_NT, ENTRY>(sk);
     for (int r = tid; r < kp1; r += SL_NT) cand[(size_t)blockIdx.x * kp1 + r] = sk[r];
     if (tid == 0) flags[blockIdx.x] = snan;
+}
+__global__ __launch_bounds__(SL_NT) void sample_slice_kernel(const float *logits, int n, const ps_sample_dev *d, float *pen, unsigned long long *cand, int *flags) {
+    sample_slice_body<0>(logits, n, d, pen, cand, flags);
 }
 
 __device__ __forceinline__ unsigned wave_incl_scan(unsigned x) {
@@ -98,224 +123,25 @@ __device__ __forceinline__ unsigned wave_incl_scan(unsigned x) {
 
 __global__ __launch_bounds__(FN_NT) void sample_final_kernel(const unsigned long long *cand, const int *flags, int nwg, const float *pen, int n,
                                                              ps_sample_dev *d, int32_t *token_out, ps_step_state *st, int32_t *tokens, int32_t *ids) {
-    __shared__ uint32_t smt[PS_MT_N];
-    __shared__ unsigned hist[256];
-    __shared__ unsigned long long sk[PS_SAMPLE_K_MAX];
-    __shared__ ps_pi heap[PS_SAMPLE_K_MAX];
-    __shared__ float tv[PS_SAMPLE_K_MAX];
-    __shared__ int32_t tt[PS_SAMPLE_K_MAX];
-    __shared__ double cp[PS_SAMPLE_K_MAX];
-    __shared__ int surv[EX_CHUNK];
-    __shared__ unsigned wsum[FN_NT / 64];
-    __shared__ uint32_t sdk[DK_CAP];
-    __shared__ double s_sum;
-    __shared__ int s_nan, s_tie, s_r, s_eq, s_cnt, s_total, s_n, s_cut, s_idx;
-    __shared__ uint32_t s_prefix, s_next;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, k = d->k, kp1 = k + 1, n_cand = nwg * kp1;
-    for (int i = tid; i < PS_MT_N; i += FN_NT) smt[i] = d->mt[i];
-    if (tid == 0) { s_nan = 0; s_tie = 0; s_cnt = 0; s_next = 0xffffffffu; }
-    __syncthreads();
-    for (int i = tid; i < nwg; i += FN_NT)
-        if (flags[i]) s_nan = 1;
-    __syncthreads();
-    bool exact = s_nan != 0;
-    if (!exact) {
-        // ---- fast path: the k-th smallest key (= k-th largest value), radix select 8 bits at a time
-        // the high halves (value keys) in LDS when they fit; each thread walks a contiguous range (runs of one sorted slice list share
-        // their digits: one LDS atomic per run instead of one per key)
-        const bool staged = n_cand <= DK_CAP;
-        if (staged) {
-            int i = tid;
-            for (; i + 3 * FN_NT < n_cand; i += 4 * FN_NT) {
-                const unsigned long long a0 = cand[i], a1 = cand[i + FN_NT], a2 = cand[i + 2 * FN_NT], a3 = cand[i + 3 * FN_NT];
-                sdk[i] = (uint32_t)(a0 >> 32); sdk[i + FN_NT] = (uint32_t)(a1 >> 32); sdk[i + 2 * FN_NT] = (uint32_t)(a2 >> 32); sdk[i + 3 * FN_NT] = (uint32_t)(a3 >> 32);
-            }
-            for (; i < n_cand; i += FN_NT) sdk[i] = (uint32_t)(cand[i] >> 32);
-        }
-        const int per = (n_cand + FN_NT - 1) / FN_NT, i0 = min(tid * per, n_cand), i1 = min(i0 + per, n_cand);
-        uint32_t prefix = 0;
-        int r = k;
-        for (int pass = 0; pass < 4; pass++) {
-            const int shift = 24 - 8 * pass;
-            for (int i = tid; i < 256; i += FN_NT) hist[i] = 0;
-            __syncthreads();
-            unsigned run_bin = 0xffffffffu, run_cnt = 0;
-            for (int i = i0; i < i1; i++) {
-                const uint32_t dk = staged ? sdk[i] : (uint32_t)(cand[i] >> 32);
-                if (pass == 0 || (dk >> (shift + 8)) == prefix) {
-                    const unsigned b = (dk >> shift) & 255;
-                    if (b == run_bin) run_cnt++;
-                    else { if (run_cnt) atomicAdd(&hist[run_bin], run_cnt); run_bin = b; run_cnt = 1; }
-                }
-            }
-            if (run_cnt) atomicAdd(&hist[run_bin], run_cnt);
-            __syncthreads();
-            if (tid < 64) {
-                unsigned h[4], s = 0;
-                for (int j = 0; j < 4; j++) { h[j] = hist[4 * tid + j]; s += h[j]; }
-                const unsigned incl = wave_incl_scan(s), excl = incl - s;
-                if (excl < (unsigned)r && incl >= (unsigned)r) { // the bin that holds rank r
-                    unsigned cum = excl;
-                    for (int j = 0; j < 4; j++) {
-                        if (cum + h[j] >= (unsigned)r) { s_r = r - (int)cum; s_prefix = (prefix << 8) | (uint32_t)(4 * tid + j); s_eq = (int)h[j]; break; }
-                        cum += h[j];
-                    }
-                }
-            }
-            __syncthreads();
-            r = s_r; prefix = s_prefix;
-        }
-        if (s_eq > r) exact = true; // the k-th and the (k+1)-th value have the same bits
-        if (!exact) {
-            uint32_t next = 0xffffffffu;
-            for (int i = i0; i < i1; i++) {
-                const uint32_t dk = staged ? sdk[i] : (uint32_t)(cand[i] >> 32);
-                if (dk <= prefix) { const int slot = atomicAdd(&s_cnt, 1); if (slot < PS_SAMPLE_K_MAX) sk[slot] = cand[i]; }
-                else next = min(next, dk);
-            }
-            atomicMin(&s_next, next);
-            __syncthreads();
-            for (int i = k + tid; i < PS_SAMPLE_K_MAX; i += FN_NT) sk[i] = ~0ull;
-            bitonic_sort_asc<PS_SAMPLE_K_MAX, FN_NT>(sk);
-            for (int i = tid; i < k; i += FN_NT) { // -0 and +0: different keys, equal values
-                const float v = ckey_val(sk[i]), w = i + 1 < k ? ckey_val(sk[i + 1]) : fkey_val(~s_next);
-                if (v == w) s_tie = 1;
-                tv[i] = v; tt[i] = (int32_t)(uint32_t)sk[i];
-            }
-            __syncthreads();
-            exact = s_tie != 0 || s_cnt != k;
-        }
-    }
-    if (exact) {
-        // ---- std::partial_sort's heap mechanics: make_heap over the first k entries, then every later entry that is greater than
-        // the top replaces it.  Only an entry greater than the top at the start of its chunk can enter (the top only rises while no
-        // NaN sits in the heap; when it falls, the rest of that chunk is walked entry by entry).
-        if (tid == 0) {
-            for (int i = 0; i < k; i++) heap[i] = ps_pi{pen[i], i};
-            ps_make_heap(heap, k);
-        }
-        __syncthreads();
-        for (int base = k; base < n; base += EX_CHUNK) {
-            const float thr = heap[0].v;
-            const int j0 = base + tid * EX_PER;
-            unsigned m = 0;
-#pragma unroll
-            for (int e = 0; e < EX_PER; e++)
-                if (j0 + e < n && pen[j0 + e] > thr) m |= 1u << e;
-            const unsigned c = __popc(m), incl = wave_incl_scan(c);
-            if (lane == 63) wsum[wave] = incl;
-            __syncthreads();
-            unsigned off = incl - c;
-            for (int w = 0; w < wave; w++) off += wsum[w];
-            for (int e = 0; e < EX_PER; e++)
-                if (m & (1u << e)) surv[off++] = j0 + e;
-            if (tid == FN_NT - 1) s_total = (int)off;
-            __syncthreads();
-            if (tid == 0) {
-                const int end = min(base + EX_CHUNK, n);
-                for (int s = 0; s < s_total; s++) {
-                    const int i = surv[s];
-                    const float v = pen[i];
-                    if (!(v > heap[0].v)) continue;
-                    ps_pop_heap_into(heap, k, ps_pi{v, i});
-                    if (heap[0].v < thr) { // the top fell below the filter's threshold: the rest of the chunk one by one
-                        for (int ii = i + 1; ii < end; ii++) {
-                            const float vv = pen[ii];
-                            if (vv > heap[0].v) ps_pop_heap_into(heap, k, ps_pi{vv, ii});
-                        }
-                        break;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            ps_sort_heap(heap, k);
-            for (int i = 0; i < k; i++) { tv[i] = heap[i].v; tt[i] = heap[i].t; }
-        }
-    }
-    __syncthreads();
-    // ---- the chain's tail (ps_sample_tail, same operations): the per-candidate steps spread over the workgroup, the ordered sums and
-    // the draw on thread 0
-    const float temp = d->temperature, top_p = d->top_p;
-    if (temp != 1)
-        for (int i = tid; i < k; i += FN_NT) tv[i] /= temp;
-    __syncthreads();
-    const float top = tv[0];
-    __syncthreads();
-    for (int i = tid; i < k; i += FN_NT) tv[i] = ps_expf_glibc(tv[i] - top);
-    __syncthreads();
-    if (tid == 0) {
-        double total = 0.;
-        for (int i = k; i-- > 0;) total += tv[i];
-        s_sum = total;
-    }
-    __syncthreads();
-    for (int i = tid; i < k; i += FN_NT) tv[i] = (float)((double)tv[i] / s_sum);
-    __syncthreads();
-    if (tid == 0) {
-        int n_keep = k, cut = 0;
-        if (top_p < 1.0f) {
-            float mass = 0.0f;
-            int keep   = 0;
-            while (keep < k) {
-                mass += tv[keep++];
-                if (mass >= top_p && keep >= 1) break;
-            }
-            if (keep < k) {
-                n_keep = keep; cut = 1;
-                double t2 = 0.;
-                for (int i = 0; i < n_keep; i++) t2 += tv[i];
-                s_sum = t2;
-            }
-        }
-        s_n = n_keep; s_cut = cut;
-    }
-    __syncthreads();
-    const int nk = s_n;
-    if (s_cut)
-        for (int i = tid; i < nk; i += FN_NT) tv[i] = (float)((double)tv[i] / s_sum);
-    __syncthreads();
-    uint64_t calls = 0;
-    uint32_t p = d->mt_pos;
-    if (nk >= 2) { // ps_discrete_draw
-        if (tid == 0) {
-            double sum = 0.0;
-            for (int i = 0; i < nk; i++) sum += (double)tv[i];
-            s_sum = sum;
-        }
-        __syncthreads();
-        for (int i = tid; i < nk; i += FN_NT) cp[i] = (double)tv[i] / s_sum;
-        __syncthreads();
-        if (tid == 0) {
-            double acc = cp[0];
-            for (int i = 1; i < nk; i++) { acc = acc + cp[i]; cp[i] = acc; }
-            cp[nk - 1] = 1.0;
-            const double u = ps_mt_canonical(smt, &p);
-            calls = 2;
-            int first = 0, len = nk;
-            while (len > 0) {
-                const int half = len >> 1, mid = first + half;
-                if (cp[mid] < u) { first = mid + 1; len = len - half - 1; }
-                else len = half;
-            }
-            s_idx = first;
-        }
-    } else if (tid == 0) {
-        s_idx = 0;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int idx = s_idx;
-        const int32_t tok = tt[idx];
-        d->mt_pos = p;
-        d->n_outputs += calls;
-        d->n_exact += exact ? 1 : 0;
-        if (token_out) token_out[0] = tok;
-        if (st) { tokens[0] = tok; ids[st->n_out] = tok; st->n_out += 1; st->pos0 += 1; }
-    }
-    __syncthreads();
-    for (int i = tid; i < PS_MT_N; i += FN_NT) d->mt[i] = smt[i];
+    constexpr int ENTRY = 0;
+#include "ps_sample_final_body.h"
+}
+// the same statements on row blockIdx.y of a batched step: the drawn id to drawn[row], that row's engine advanced, nothing else
+__global__ __launch_bounds__(FN_NT) void sample_final_rows_kernel(int nwg, int n, ps_sample_dev *devs, char *scratch, size_t row_bytes, int32_t *drawn) {
+    const sample_scratch s = sample_carve(scratch + (size_t)blockIdx.y * row_bytes, nwg, n);
+    const unsigned long long *cand = s.cand;
+    const int *flags = s.flags;
+    const float *pen = s.pen;
+    ps_sample_dev *d = devs + blockIdx.y;
+    int32_t *token_out = drawn + blockIdx.y, *tokens = nullptr, *ids = nullptr;
+    ps_step_state *st = nullptr;
+    constexpr int ENTRY = 1;
+#include "ps_sample_final_body.h"
+}
+__global__ __launch_bounds__(SL_NT) void sample_slice_rows_kernel(const float *logits, int n, int64_t row_stride, const ps_sample_dev *devs, char *scratch, size_t row_bytes) {
+    const int row = blockIdx.y;
+    const sample_scratch s = sample_carve(scratch + (size_t)row * row_bytes, (int)gridDim.x, n);
+    sample_slice_body<1>(logits + (int64_t)row * row_stride, n, devs + row, s.pen, s.cand, s.flags);
 }
 
 const char *g_last_sample = "";
@@ -330,12 +156,17 @@ size_t psl_sample_scratch_bytes(int n_vocab) {
 }
 void psl_sample(hipStream_t st, const float *logits, int n, ps_sample_dev *d, void *scratch, int32_t *token_out, ps_step_state *state, int32_t *tokens, int32_t *ids) {
     const int nwg = slices(n);
-    unsigned long long *cand = (unsigned long long *)scratch;
-    float *pen = (float *)(cand + (size_t)nwg * (PS_SAMPLE_K_MAX + 1));
-    int *flags = (int *)(pen + n);
+    const sample_scratch s = sample_carve(scratch, nwg, n);
     g_last_sample = "sample_slice_kernel + sample_final_kernel";
-    hipLaunchKernelGGL(sample_slice_kernel, dim3((unsigned)nwg), dim3(SL_NT), 0, st, logits, n, d, pen, cand, flags);
-    hipLaunchKernelGGL(sample_final_kernel, dim3(1), dim3(FN_NT), 0, st, cand, flags, nwg, pen, n, d, token_out, state, tokens, ids);
+    hipLaunchKernelGGL(sample_slice_kernel, dim3((unsigned)nwg), dim3(SL_NT), 0, st, logits, n, d, s.pen, s.cand, s.flags);
+    hipLaunchKernelGGL(sample_final_kernel, dim3(1), dim3(FN_NT), 0, st, s.cand, s.flags, nwg, s.pen, n, d, token_out, state, tokens, ids);
+}
+void psl_sample_rows(hipStream_t st, const float *logits, int n, int64_t row_stride, int rows, ps_sample_dev *devs, void *scratch, int32_t *drawn) {
+    const int nwg = slices(n);
+    const size_t row_bytes = psl_sample_scratch_bytes(n);
+    g_last_sample = "sample_slice_rows_kernel + sample_final_rows_kernel";
+    hipLaunchKernelGGL(sample_slice_rows_kernel, dim3((unsigned)nwg, (unsigned)rows), dim3(SL_NT), 0, st, logits, n, row_stride, devs, (char *)scratch, row_bytes);
+    hipLaunchKernelGGL(sample_final_rows_kernel, dim3(1, (unsigned)rows), dim3(FN_NT), 0, st, nwg, n, devs, (char *)scratch, row_bytes, drawn);
 }
 
 int psl_sample_pack(const ps_sample_cfg *c, const ps_sample_state *s, int n_vocab, ps_sample_dev *out, std::string *err) {
@@ -400,6 +231,35 @@ int ps_hip_sample(ps_hip_ctx *c, const float *logits_dev, int n_vocab, const ps_
     (void)hipFree(dd); (void)hipFree(scratch);
     if (e != hipSuccess) { c->err = std::string("sample: ") + hipGetErrorString(e); return 1; }
     psl_sample_unpack(&h, state);
+    return 0;
+}
+
+int ps_hip_sample_rows(ps_hip_ctx *c, const float *logits_dev, int n_vocab, int64_t row_stride, int rows, const ps_sample_cfg *cfgs, ps_sample_state *states, int32_t *tokens_out) {
+    if (rows < 1 || rows > PS_SEQ_COLS_MAX) PS_FAIL(c, "sample_rows: 1 <= rows <= 16");
+    if (!logits_dev || !cfgs || !states || !tokens_out) PS_FAIL(c, "sample_rows: null argument");
+    if (row_stride < (int64_t)n_vocab) PS_FAIL(c, "sample_rows: row_stride < n_vocab");
+    std::vector<ps_sample_dev> h((size_t)rows); // every row packed before anything reaches the device: a refusal has changed nothing
+    for (int r = 0; r < rows; r++) {
+        std::string err;
+        if (int rc = psl_sample_pack(cfgs + r, states + r, n_vocab, &h[r], &err)) { c->err = "sample_rows: row " + std::to_string(r) + ": " + err; return rc; }
+    }
+    PS_CHECK(c, hipSetDevice(c->device));
+    const size_t dev_bytes = (size_t)rows * sizeof(ps_sample_dev);
+    void *dd = nullptr, *scratch = nullptr;
+    PS_CHECK(c, hipMalloc(&dd, dev_bytes + 64));
+    if (hipMalloc(&scratch, (size_t)rows * psl_sample_scratch_bytes(n_vocab)) != hipSuccess) { (void)hipFree(dd); PS_FAIL(c, "sample_rows: scratch allocation failed"); }
+    int32_t *tok_dev = (int32_t *)((char *)dd + dev_bytes);
+    hipError_t e = hipMemcpyAsync(dd, h.data(), dev_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        psl_sample_rows(c->stream, logits_dev, n_vocab, row_stride, rows, (ps_sample_dev *)dd, scratch, tok_dev);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), dd, dev_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tokens_out, tok_dev, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(dd); (void)hipFree(scratch);
+    if (e != hipSuccess) { c->err = std::string("sample_rows: ") + hipGetErrorString(e); return 1; }
+    for (int r = 0; r < rows; r++) psl_sample_unpack(&h[r], states + r);
     return 0;
 }
 

@@ -88,6 +88,8 @@ struct ps_hip_model {
     step_graph graphs[G_COUNT];            // the captured single-token steps (dropped together: drop_graphs)
     ps_sample_dev *sample_dev = nullptr;   // sampler configuration + engine state of the current sampled run (allocated at first use)
     void *sample_scratch = nullptr;
+    ps_sample_dev *sample_devs = nullptr;  // [min(16, max_batch)] one per column of a sampled batched run (ps_hip_model_decode_batch_sampled; allocated at first use),
+    void *sample_rows_scratch = nullptr;   // and as many scratches of psl_sample_scratch_bytes
     void *score_scratch = nullptr;         // scoring (ps_hip_model_score; allocated at first use): k_score.hip's scratch for max_batch rows,
     int32_t *score_targets = nullptr;      // [max_batch] the targets of the forward's columns,
     ps_score *score_out = nullptr;         // [max_batch] their records
@@ -250,7 +252,7 @@ struct fwd_opts {
     bool tree = false;     // tree_dev is the attention's mask
     bool rope_pos = false; // RoPE positions from rope_pos_dev (a tree forward)
     bool advance = false;  // with lm_head: the step feeds its own id back and moves the device-side state on (the decode loops)
-    bool sampled = false;  // with lm_head: the sampler chain (sample_dev) in place of the arg-max
+    bool sampled = false;  // with lm_head: the sampler chain (sample_dev; with sq: column i's own, sample_devs[i]) in place of the arg-max
     bool score = false;    // with lm_head: every column scored against score_targets (k_score.hip) in place of the arg-max
     // sq: a batched decode step -- column i is a token of ITS OWN sequence (sq->tab); the mat-muls are the column-wise ones of any batch, RoPE + KV append and the
     // attention go per column to that sequence's cache (k_attn.hip, "batched decode")
@@ -411,7 +413,10 @@ static int enqueue_forward(ps_hip_model *m, int bs, const fwd_opts &o) {
         if (mm(m, mm_args(m, MM_LM_HEAD, 0), act_for(dim), dim, bs)) return 2;
         const bool advance = o.advance;
         if (o.score) psl_score(st, m->logits, (int)f.vocab_size, (int64_t)f.vocab_size, bs, m->score_targets, m->score_scratch, m->score_out);
-        else if (o.sampled) psl_sample(st, m->logits, (int)f.vocab_size, m->sample_dev, m->sample_scratch, nullptr, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
+        else if (sq && o.sampled) { // column i draws from its own chain; the drawn ids take the arg-max's place in the batched step's bookkeeping
+            psl_sample_rows(st, m->logits, (int)f.vocab_size, (int64_t)f.vocab_size, bs, m->sample_devs, m->sample_rows_scratch, m->argmax_dev);
+            if (advance) psl_seqs_advance(st, m->seq_tab, m->argmax_dev, m->tokens_dev, m->seq_ids_dev, bs);
+        } else if (o.sampled) psl_sample(st, m->logits, (int)f.vocab_size, m->sample_dev, m->sample_scratch, nullptr, advance ? m->state : nullptr, m->tokens_dev, m->ids_dev);
         else if (sq) {
             psl_argmax2(st, m->logits, f.vocab_size, bs, m->argmax_dev, m->am_v, m->am_i, nullptr, nullptr, nullptr);
             if (advance) psl_seqs_advance(st, m->seq_tab, m->argmax_dev, m->tokens_dev, m->seq_ids_dev, bs);
@@ -1096,6 +1101,41 @@ int ps_hip_model_decode_batch_greedy(ps_hip_model *m, const int32_t *seq_ids, co
     }
     PS_CHECK(c, hipMemcpyAsync(out_ids, m->seq_ids_dev, (size_t)steps * n * 4, hipMemcpyDeviceToHost, c->stream));
     PS_CHECK(c, sync_stream(m));
+    batch_advance(m, seq_ids, n, (size_t)steps);
+    return 0;
+}
+// The same loop with every column fed the token its own sampler chain drew (k_sample.hip's rows kernels behind the lm_head; DESIGN.md "Sampled batched decode").  Every
+// column is packed before anything is uploaded: a column that is not covered refuses the whole call.  The chains go to the device once and come back once.
+int ps_hip_model_decode_batch_sampled(ps_hip_model *m, const int32_t *seq_ids, const int32_t *tokens, int n, int steps, const ps_sample_cfg *cfgs, ps_sample_state *states,
+                                      int32_t *out_ids) {
+    ps_hip_ctx *c = m->ctx;
+    if (steps <= 0) return 0;
+    if (int rc = settle_pending(m)) return rc;
+    if (int rc = batch_check(m, seq_ids, tokens, n, steps, "decode_batch_sampled")) return rc;
+    if (!cfgs || !states || !out_ids) PS_FAIL(c, "decode_batch_sampled: null argument");
+    std::vector<ps_sample_dev> h((size_t)n); // (staging of the chains' upload / read-back; the stream is idle between the two)
+    for (int i = 0; i < n; i++) {
+        std::string err;
+        if (psl_sample_pack(cfgs + i, states + i, (int)m->cfg.vocab_size, &h[i], &err)) PS_FAIL(c, "decode_batch_sampled: column " + std::to_string(i) + ": " + err);
+    }
+    PS_CHECK(c, hipSetDevice(c->device));
+    const size_t cap = (size_t)(m->max_batch < PS_SEQ_COLS_MAX ? m->max_batch : PS_SEQ_COLS_MAX);
+    if (!m->sample_devs && dmalloc(m, (void **)&m->sample_devs, cap * sizeof(ps_sample_dev))) return 1;
+    if (!m->sample_rows_scratch && dmalloc(m, &m->sample_rows_scratch, cap * psl_sample_scratch_bytes((int)m->cfg.vocab_size))) return 1;
+    psl_seqs_args sq{};
+    if (int rc = batch_begin(m, seq_ids, tokens, n, &sq)) return rc;
+    PS_CHECK(c, hipMemcpyAsync(m->sample_devs, h.data(), (size_t)n * sizeof(ps_sample_dev), hipMemcpyHostToDevice, c->stream));
+    const int top0 = sq.n_kv_max;
+    fwd_opts o;
+    o.lm_head = true; o.advance = true; o.sampled = true; o.sq = &sq;
+    for (int s = 0; s < steps; s++) {
+        sq.n_kv_max = top0 + s;
+        if (int rc = enqueue_forward(m, n, o)) { (void)sync_stream(m); return rc; }
+    }
+    PS_CHECK(c, hipMemcpyAsync(out_ids, m->seq_ids_dev, (size_t)steps * n * 4, hipMemcpyDeviceToHost, c->stream));
+    PS_CHECK(c, hipMemcpyAsync(h.data(), m->sample_devs, (size_t)n * sizeof(ps_sample_dev), hipMemcpyDeviceToHost, c->stream));
+    PS_CHECK(c, sync_stream(m));
+    for (int i = 0; i < n; i++) psl_sample_unpack(&h[i], states + i);
     batch_advance(m, seq_ids, n, (size_t)steps);
     return 0;
 }

@@ -127,6 +127,9 @@ size_t psl_sample_scratch_bytes(int n_vocab);
 // penalty + top-k + tail + draw of one row of n logits; token_out (device) optional; with state != NULL also the decode
 // bookkeeping of psl_argmax2: token[0] = id, ids[state->n_out++] = id, state->pos0++
 void psl_sample(hipStream_t st, const float *logits, int n, ps_sample_dev *d, void *scratch, int32_t *token_out, ps_step_state *state, int32_t *tokens, int32_t *ids);
+// the same chain on `rows` rows in one pair of launches: row r of n logits at logits + r * row_stride (any alignment) with devs[r], its own scratch of
+// psl_sample_scratch_bytes(n) at scratch + r * that, its id to drawn[r] (device).  No bookkeeping: a batched step feeds drawn[] to psl_seqs_advance
+void psl_sample_rows(hipStream_t st, const float *logits, int n, int64_t row_stride, int rows, ps_sample_dev *devs, void *scratch, int32_t *drawn);
 
 // scoring (k_score.hip): three launches over rows x n logits (row r at logits + r * stride), targets and records on the device; then, with the records on the
 // host and the stream idle, psl_score_finish redoes the flagged rows exactly and counts

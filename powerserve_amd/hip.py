@@ -38,6 +38,7 @@ EXPORTS = [
     "ps_hip_score_rows", "ps_hip_model_score", "ps_hip_score_counters",
     "ps_hip_model_create_long", "ps_hip_model_is_long", "ps_hip_softmax_long_counters",
     "ps_hip_model_seq_fork", "ps_hip_model_seq_state_bytes", "ps_hip_model_seq_export", "ps_hip_model_seq_import",
+    "ps_hip_sample_rows", "ps_hip_model_decode_batch_sampled",
 ]
 LONG_CTX_MAX = 131072  # PS_HIP_LONG_CTX_MAX (include/ps_hip.h)
 DEBUG_LONG_PV_TILE, DEBUG_LONG_EPS_SHIFT = 13, 14  # ps_hip_debug_set keys: attn_pv_long_kernel's tile (positions), the long soft-max certificate's eps x 2^value
@@ -186,6 +187,7 @@ def lib() -> C.CDLL:
         "ps_hip_softmax_long_counters": (None, [vp, i32]),
         "ps_hip_model_seq_fork": (i32, [vp, i32, vp, i32, sz]), "ps_hip_model_seq_state_bytes": (sz, [vp, sz]),
         "ps_hip_model_seq_export": (i32, [vp, i32, sz, vp, sz]), "ps_hip_model_seq_import": (i32, [vp, i32, vp, sz]),
+        "ps_hip_sample_rows": (i32, [vp, vp, i32, i64, i32, vp, vp, vp]), "ps_hip_model_decode_batch_sampled": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
         "ps_hip_debug_f16_gemm": (i32, [vp, i32, C.c_int64, C.c_int64, i32, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -545,6 +547,19 @@ class Model:
         self.ctx.check(self.ctx.L.ps_hip_model_decode_batch_greedy(self.h, _ptr(seq_ids), _ptr(tokens), tokens.size, int(steps), _ptr(out)))
         return out
 
+    def decode_batch_sampled(self, seq_ids, tokens, steps: int, cfgs, states) -> np.ndarray:
+        """decode_batch_greedy with column i fed the token its own chain drew (cfgs[i], states[i]): ids [steps][n]; every states[i] is advanced in place."""
+        seq_ids = np.ascontiguousarray(seq_ids, dtype=np.int32)
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        if not (seq_ids.size == tokens.size == len(cfgs) == len(states)):
+            raise ValueError("decode_batch_sampled: one token, one configuration and one state per sequence")
+        n = tokens.size
+        ca, sa = _struct_array(SampleCfg, cfgs), _struct_array(SampleState, states)
+        out = np.empty((max(int(steps), 0), n), dtype=np.int32)
+        self.ctx.check(self.ctx.L.ps_hip_model_decode_batch_sampled(self.h, _ptr(seq_ids), _ptr(tokens), n, int(steps), ca, sa, _ptr(out)))
+        _struct_array_back(sa, states)
+        return out
+
     # ---- fork / save / restore (include/ps_hip.h ps_hip_model_seq_fork / _export / _import)
     def seq_fork(self, src: int, dsts, n_tokens: int | None = None):
         """Slots [0, n_tokens) of sequence src into every sequence of dsts (one launch); n_tokens None: src's whole history."""
@@ -608,6 +623,32 @@ def sample(ctx: Ctx, logits_dev: int, n_vocab: int, cfg: SampleCfg, state: Sampl
     tok = C.c_int32(-1)
     ctx.check(ctx.L.ps_hip_sample(ctx.h, C.c_void_p(logits_dev), int(n_vocab), C.byref(cfg), C.byref(state), C.byref(tok)))
     return int(tok.value)
+
+
+def _struct_array(cls, items):
+    """a contiguous ctypes array holding copies of `items` (the C-ABI takes arrays of structs)"""
+    a = (cls * max(len(items), 1))()
+    for i, x in enumerate(items):
+        C.memmove(C.byref(a, i * C.sizeof(cls)), C.byref(x), C.sizeof(cls))
+    return a
+
+
+def _struct_array_back(a, items):
+    for i, x in enumerate(items):
+        C.memmove(C.byref(x), C.byref(a, i * C.sizeof(type(x))), C.sizeof(type(x)))
+
+
+def sample_rows(ctx: Ctx, logits_dev: int, n_vocab: int, row_stride: int, cfgs, states) -> np.ndarray:
+    """sample() for len(cfgs) rows of device logits in one pair of launches (row r at logits_dev + 4 * r * row_stride bytes, cfgs[r], states[r]): the drawn
+    tokens; every states[r] is advanced in place."""
+    if len(cfgs) != len(states):
+        raise ValueError("sample_rows: one configuration and one state per row")
+    rows = len(cfgs)
+    ca, sa = _struct_array(SampleCfg, cfgs), _struct_array(SampleState, states)
+    out = np.full(max(rows, 1), -1, dtype=np.int32)
+    ctx.check(ctx.L.ps_hip_sample_rows(ctx.h, C.c_void_p(logits_dev), int(n_vocab), int(row_stride), rows, ca, sa, _ptr(out)))
+    _struct_array_back(sa, states)
+    return out[:rows]
 
 
 def sample_covered(cfg: SampleCfg, n_vocab: int, state: SampleState | None = None) -> bool:

@@ -19,7 +19,8 @@ EXPORTS = ["psh_last_error", "psh_model_load", "psh_model_free", "psh_model_set_
            "psh_debug_std_mt_seed", "psh_debug_std_discrete", "psh_debug_std_partial_sort",
            "psh_model_score", "psh_ppl_create", "psh_ppl_destroy", "psh_ppl_add", "psh_ppl_current", "psh_ppl_logit_sum", "psh_ppl_n_tokens", "psh_debug_score_row", "psh_debug_score_certify",
            "psh_model_load_long", "psh_debug_softmax_long_sum",
-           "psh_model_seq_fork", "psh_model_seq_export", "psh_model_seq_import", "psh_debug_kv_state_check", "psh_debug_kv_state_header"]
+           "psh_model_seq_fork", "psh_model_seq_export", "psh_model_seq_import", "psh_debug_kv_state_check", "psh_debug_kv_state_header",
+           "psh_model_decode_batch_sampled"]
 _LIB = None
 
 
@@ -61,6 +62,7 @@ def lib() -> C.CDLL:
         L.psh_model_seq_position.restype = C.c_int64
         L.psh_model_seq_position.argtypes = [C.c_void_p, C.c_int]
         L.psh_model_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.psh_model_decode_batch_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.psh_graph_softmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.psh_backend_get_n_tasks.argtypes = [C.c_void_p]
         L.psh_backend_add_cache.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
@@ -241,6 +243,19 @@ class HostModel:
         if self.L.psh_model_decode_batch(self.h, s.ctypes.data, t.ctypes.data, t.size, ids.ctypes.data, lg.ctypes.data if want_logits else None):
             raise HostError(self.L.psh_last_error().decode())
         return (ids, lg) if want_logits else ids
+
+    def decode_batch_sampled(self, seq_ids, tokens, steps: int, samplers) -> np.ndarray:
+        """Model::decode_batch_sampled: `steps` batched steps, column i fed the token samplers[i] (a Sampler) drew; ids [steps][n].  Standard chains the device covers
+        run on the device in one call, anything else makes the whole call the host loop; the chains end in the same state either way."""
+        s = np.ascontiguousarray(seq_ids, dtype=np.int32)
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        if not (s.size == t.size == len(samplers)) or t.size == 0:
+            raise ValueError("decode_batch_sampled: one token and one sampler per sequence, at least one")
+        ids = np.empty((max(int(steps), 0), t.size), dtype=np.int32)
+        chains = (C.c_void_p * t.size)(*[c.h for c in samplers])
+        if self.L.psh_model_decode_batch_sampled(self.h, s.ctypes.data, t.ctypes.data, t.size, int(steps), chains, ids.ctypes.data):
+            raise HostError(self.L.psh_last_error().decode())
+        return ids
 
     # ---- fork / save / restore (Model::fork_sequence / export_sequence / import_sequence)
     def fork_sequence(self, src: int, dsts, n_tokens: int | None = None):
